@@ -2,6 +2,8 @@
 """Benchmark of the multiview ground-plane fusion path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --full                             (+ everything below that is not the headline)
+    python bench.py ... --dump-outputs DIR                 (the last timed step's outputs as DIR/<name>.npy)
 
 One step = one multiview frame: N_cam synthetic views [1, N_cam, 3, 720, 1280] already resident in
 HBM -> ResNet-18 trunk + heads (PyTorch-ROCm) -> homography warp (HIP) -> shadow transformer with
@@ -9,7 +11,10 @@ HBM -> ResNet-18 trunk + heads (PyTorch-ROCm) -> homography warp (HIP) -> shadow
 pretrained download or the datasets).  This is BASELINE.json configs[1], "Wildtrack 7-cam,
 --world_feat deform_trans, ResNet18, 1 x MI355X".
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline: metric/value,
+ms_per_step, config, roofline (its main entry: the HIP events of the timed steps themselves) and startup.  The rest --
+hot_path, roofline's init_weights / uncalibrated_offsets / spread_sweep, the other kernels' rooflines and cpu_baseline --
+takes runs of its own and is measured with --full only (null otherwise; the --no-* switches still apply under --full).
   metric/value     multiview frames/s, whole job (all ranks)
   roofline         (input: the model's sampling-offset / attention projections are seeded stand-ins for learned ones, calibrated
                    layer by layer on the model's own queries so that the learned part of the offsets has SURVEY 8d's spread of
@@ -71,10 +76,15 @@ def parse():
                     help="--parallel views only: shadow transformer partitioned by camera, or replicated")
     ap.add_argument("--batch", type=int, default=1, help="frames per step per rank (dp mode; the reference only supports 1)")
     ap.add_argument("--augment", action="store_true", help="random affine augmentation matrices instead of identity")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (hot path alone, the forward on other weights, the other "
+                         "kernels' rooflines, the CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed frames and the hot-path runs: no init-weight / uncalibrated / spread-sweep runs and none of the "
-                         "other kernels' rooflines -- what tools/profile_bench.sh traces so that rocprofv3's average of the forward kernel "
+                    help="with --full: only the timed frames and the hot-path runs: no init-weight / uncalibrated / spread-sweep runs and none of "
+                         "the other kernels' rooflines -- what tools/profile_bench.sh traces so that rocprofv3's average of the forward kernel "
                          "covers the SAME launches as `roofline.avg_launch_us` (every other run in this file launches that kernel on another input)")
     ap.add_argument("--no-kernel-rooflines", action="store_true",
                     help="skip roofline_warp / roofline_warp_bwd / roofline_msda_bwd (measured after the timed region)")
@@ -134,9 +144,18 @@ def calibrate_sampling(attn_layers, run_once, std_px):
 
         def hook(mod, args, kwargs, seen=seen):
             q = args[0] if args else kwargs["query"]
-            with torch.no_grad():
-                seen["off"] = float(torch.nn.functional.linear(q, mod.sampling_offsets.weight).float().std())
-                seen["logit"] = float(torch.nn.functional.linear(q, mod.attention_weights.weight).float().std())
+            # these two products only measure a spread and never run in a step: TunableOp does not tune their shapes
+            # (~2.5 s of a fresh process's start-up); the step's own GEMMs are tuned as before
+            tuning = q.is_cuda and torch.cuda.tunable.tuning_is_enabled()
+            if tuning:
+                torch.cuda.tunable.tuning_enable(False)
+            try:
+                with torch.no_grad():
+                    seen["off"] = float(torch.nn.functional.linear(q, mod.sampling_offsets.weight).float().std())
+                    seen["logit"] = float(torch.nn.functional.linear(q, mod.attention_weights.weight).float().std())
+            finally:
+                if tuning:
+                    torch.cuda.tunable.tuning_enable(True)
 
         h = at.register_forward_pre_hook(hook, with_kwargs=True)
         try:
@@ -343,6 +362,33 @@ def write_tunableop_results(tun, path):
     os.replace(tmp, path)
 
 
+def step_outputs(out):
+    """What a caller of the timed step receives, by name: the model's ((world_heatmap, world_offset), (imgs_heatmap,
+    imgs_offset, imgs_wh)), or the view-sharded frame's (world_heatmap, world_offset)."""
+    if isinstance(out[0], (tuple, list)):
+        (wh, wo), (ih, io, iw) = out
+        return {"world_heatmap": wh, "world_offset": wo, "imgs_heatmap": ih, "imgs_offset": io, "imgs_wh": iw}
+    return {"world_heatmap": out[0], "world_offset": out[1]}
+
+
+def dump_outputs(arrays, out_dir, budget_bytes=64 << 20, seed=0):
+    """Every array as out_dir/<name>.npy, float32 (float64 stays float64).  Past `budget_bytes` in all, each array is
+    replaced by the same fixed, seeded sample of its flattened elements (sorted indices; the same fraction of every
+    array), so that two runs with the same arguments write comparable files."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    frac = budget_bytes / total if total > budget_bytes else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        if frac < 1.0:
+            flat = v.reshape(-1)
+            n = int(flat.size * frac)
+            v = flat[np.sort(np.random.default_rng(seed).choice(flat.size, n, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def load_traffic():
     """HBM-side bytes per call of the path's kernels from the newest committed PMC summary (profiles/*_traffic.json,
     written by tools/profile_bench.sh): ({"msda_fwd": bytes, "warp_fwd": ..., "warp_bwd": ..., "msda_bwd": ...}, file)."""
@@ -450,6 +496,10 @@ def main():
         raise SystemExit("bench.py needs a GPU (the HIP kernels have no CPU fallback)")
     dev = torch.device("cuda", local_rank % torch.cuda.device_count())
     torch.cuda.set_device(dev)
+    # MIOpen's search also compiles and times its naive reference convolution for every shape: ~20 s of a fresh process's
+    # start-up, for a kernel 10-50x slower than the one picked for each of this model's convolutions on MI355X.  Leaving it
+    # out of the search changes neither the picks nor the step time (measured).  (Set here, not at import: only this process.)
+    os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "0")
     torch.backends.cudnn.benchmark = True      # the reference's own setting (main.py:48): MIOpen picks convolutions by measurement
     gemm_tuning = False
     if not a.no_gemm_tuning:
@@ -589,6 +639,8 @@ def main():
     elapsed = mdist.barrier_and_max(time.perf_counter() - t0, dev)
     timer.enabled = False
     clock.mark("timed_steps")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(out), a.dump_outputs)
     k_us, k_n, k_bytes = timer.average_us()
     impl = MSDA.last_forward_kernel()
     fwd_resources = MSDA.last_forward_resources()          # registers / scratch (spill) bytes per lane / static LDS of that instantiation
@@ -610,7 +662,7 @@ def main():
 
     # ---- the hot path alone (warp + shadow transformer), same inputs ------------------------------------
     hot_ms = None
-    if a.parallel == "dp":
+    if a.full and a.parallel == "dp":
         with torch.no_grad():
             feat = model.features(imgs)
             proj = model.frame_proj_mats(M, dev)
@@ -625,7 +677,7 @@ def main():
 
     # ---- the same kernel on the reference's initial (zero) offset / attention weights, for comparison ---------------
     init_us = None
-    if a.parallel == "dp" and offset_std and attn_layers and not a.headline_only:
+    if a.full and a.parallel == "dp" and offset_std and attn_layers and not a.headline_only:
         saved = [(at.sampling_offsets.weight.detach().clone(), at.attention_weights.weight.detach().clone()) for at in attn_layers]
         with torch.no_grad():
             for at in attn_layers:
@@ -649,7 +701,7 @@ def main():
 
     # ---- and on the UNCALIBRATED perturbation (rounds 2 - 4a quoted `roofline` on it: like for like with those lines) ----
     uncal_us = None
-    if a.parallel == "dp" and uncalibrated and attn_layers and not a.headline_only:
+    if a.full and a.parallel == "dp" and uncalibrated and attn_layers and not a.headline_only:
         saved = [(at.sampling_offsets.weight.detach().clone(), at.attention_weights.weight.detach().clone()) for at in attn_layers]
         with torch.no_grad():
             for at, (ow, aw) in zip(attn_layers, uncalibrated):
@@ -674,7 +726,7 @@ def main():
     # ---- how the same kernel degrades with the spread of the learned offsets: the calibrated (1 px) offset projections scaled
     #      to 0.5 / 1 / 2 / 4 px, in the model (exact for the first layer; later layers' queries move a little with it) ----------
     spread_sweep = None
-    if a.parallel == "dp" and offset_calibration and attn_layers and not a.no_kernel_rooflines and not a.headline_only:
+    if a.full and a.parallel == "dp" and offset_calibration and attn_layers and not a.no_kernel_rooflines and not a.headline_only:
         saved = [at.sampling_offsets.weight.detach().clone() for at in attn_layers]
         spread_sweep = {}
         with torch.no_grad():
@@ -750,7 +802,7 @@ def main():
                      "frames_per_s": round(1e3 / hot_ms, 1) if hot_ms else None,
                      "what": "warp_perspective + DeformTransWorldFeat (3 x MSDeformAttn), features resident"},
     }
-    if a.parallel == "dp" and not a.no_kernel_rooflines and not a.headline_only and hasattr(model.world_feat, "encoder"):
+    if a.full and a.parallel == "dp" and not a.no_kernel_rooflines and not a.headline_only and hasattr(model.world_feat, "encoder"):
         res.update(other_kernel_rooflines(model, geom, feat, proj, MSDA))
         for key, tkey in (("roofline_warp", "warp_fwd"), ("roofline_warp_bwd", "warp_bwd"), ("roofline_msda_bwd", "msda_bwd"),
                           ("roofline_train_step", "msda_train")):
@@ -771,7 +823,7 @@ def main():
     for k, e in res.items():
         if k.startswith("roofline"):
             add_ratio(e)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(model, imgs[:1].cpu(), model.frame_proj_mats(M[:1]), a.cpu_budget_s)
         clock.mark("cpu_baseline")
     else:

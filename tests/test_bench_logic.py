@@ -1,5 +1,6 @@
-"""CPU checks of bench.py's host logic: the self-launch command for --gpus N, and that the seeded stand-in for learned
-sampling offsets really produces the spread SURVEY 8d names (bias grid + ~N(0, 1 px)) on the model's own tokens."""
+"""CPU checks of bench.py's host logic: the self-launch command for --gpus N, that the seeded stand-in for learned
+sampling offsets really produces the spread SURVEY 8d names (bias grid + ~N(0, 1 px)) on the model's own tokens, and what
+--full / --dump-outputs do."""
 import os
 import sys
 import types
@@ -97,3 +98,38 @@ def test_calibration_brings_every_layers_offset_spread_to_the_target():
     for hk in hooks:
         hk.remove()
     assert all(abs(s - 1.0) < 0.05 for s in spreads), spreads
+
+
+def test_a_plain_run_leaves_the_extra_measurements_to_full(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 5 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_every_output_and_keeps_to_the_budget(tmp_path):
+    import numpy as np
+    g = torch.Generator().manual_seed(0)
+    out = ((torch.randn(1, 1, 12, 36, generator=g), torch.randn(1, 2, 12, 36, generator=g)),
+           (torch.randn(7, 1, 9, 16, generator=g), torch.randn(7, 2, 9, 16, generator=g), torch.randn(7, 2, 9, 16, generator=g)))
+    named = bench.step_outputs(out)
+    assert list(named) == ["world_heatmap", "world_offset", "imgs_heatmap", "imgs_offset", "imgs_wh"]
+    assert list(bench.step_outputs(out[0])) == ["world_heatmap", "world_offset"]          # (the view-sharded frame's pair)
+    bench.dump_outputs(named, str(tmp_path / "all"))
+    for k, v in named.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.numpy())
+    # past the budget: the same seeded sample of every array, run after run, within the budget
+    budget = 4096
+    for d in ("a", "b"):
+        bench.dump_outputs(named, str(tmp_path / d), budget_bytes=budget)
+    sizes = 0
+    for k, v in named.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b) and 0 < a.size < v.numel() and np.isin(a, v.numpy().ravel()).all()
+        sizes += a.nbytes
+    assert sizes <= budget
+    bench.dump_outputs({"x": torch.ones(3, dtype=torch.float64)}, str(tmp_path / "f64"))
+    assert np.load(tmp_path / "f64" / "x.npy").dtype == np.float64

@@ -6,7 +6,7 @@ for mode in 2 default; do
   export MIOPEN_USER_DB_PATH=/tmp/miopen_db_$mode MIOPEN_CUSTOM_CACHE_DIR=/tmp/miopen_cache_$mode
   mkdir -p $MIOPEN_USER_DB_PATH $MIOPEN_CUSTOM_CACHE_DIR
   if [ $mode = default ]; then unset MIOPEN_FIND_MODE; else export MIOPEN_FIND_MODE=$mode; fi
-  ( time python bench.py --no-cpu-baseline ) > $O/bench_mode_$mode.log 2>&1
+  ( time python bench.py --full --no-cpu-baseline ) > $O/bench_mode_$mode.log 2>&1
   grep '^{' $O/bench_mode_$mode.log | tail -1 > $O/bench_mode_$mode.json
   python - $O/bench_mode_$mode.json <<'PY'
 import json,sys

@@ -3,7 +3,7 @@
 #   /usr/local/graft/bin/gpurun --timeout 1800 -- 'bash tools/gpu.sh <task> [args] > gpurun_out/<task>.log 2>&1'
 # Tasks:
 #   tests [pytest args]         the GPU suite (default: everything marked gpu)
-#   bench [bench.py args]       the contract benchmark, one JSON line + a short digest
+#   bench [bench.py args]       the contract benchmark with --full, one JSON line + a short digest
 #   micro [config] [iters]      kernel-level timings (tools/microbench.py) of wildtrack | multiviewx | stress16
 #   ab_bwd                      MSDA backward, every MVDETR_MSDA_BWD_IMPL x {wildtrack, multiviewx} + kernel trace per route
 #   ab_lib lib1.so lib2.so ...  the microbenchmark under other builds of the library (mvdetr_amd/csrc/<lib>; "" = default)
@@ -24,7 +24,7 @@ trace_of() {   # trace_of <filter> <env assignments...> -- <command...>
 case $task in
 tests) python -m pytest tests -m gpu -x -q "$@" 2>&1 | tail -8 ;;
 bench)
-  ( time python bench.py "$@" ) > $O/bench_run.log 2>&1
+  ( time python bench.py --full "$@" ) > $O/bench_run.log 2>&1
   grep '^{' $O/bench_run.log | tail -1 > $O/bench_line.json
   python - <<'PY'
 import json, os

@@ -27,12 +27,12 @@ def bench_tables(tag):
     if raw is None:
         return [f"*(profiles/{tag}_bench.json is missing)*"]
     d = json.loads(raw.strip().splitlines()[-1])
-    out = [f"**`python bench.py` on one MI355X** (`profiles/{tag}_bench.json`): **{d['value']} {d['unit']}** "
+    out = [f"**`python bench.py --full` on one MI355X** (`profiles/{tag}_bench.json`): **{d['value']} {d['unit']}** "
            f"({d['ms_per_step']} ms per frame, {d['steps']} timed steps, n_gpus {d['n_gpus']}, dtype {d['dtype']}); hot path alone "
            f"(warp + shadow transformer, features resident) **{d['hot_path']['ms_per_frame']} ms/frame**; CPU baseline "
            f"({d['cpu_baseline']['kind']}, {d['cpu_baseline']['cores']} threads) {d['cpu_baseline']['value']} frames/s."
            if d.get("cpu_baseline") else
-           f"**`python bench.py`** (`profiles/{tag}_bench.json`): {d['value']} {d['unit']}.", ""]
+           f"**`python bench.py --full`** (`profiles/{tag}_bench.json`): {d['value']} {d['unit']}.", ""]
     out += ["| bench.py key | kernel(s) | avg µs (HIP events) | algorithmic bytes / launch | GB/s | % of 8 TB/s | launches |",
             "|---|---|---|---|---|---|---|"]
     for key in ("roofline", "roofline_iid_offsets", "roofline_warp", "roofline_warp_bwd", "roofline_msda_bwd", "roofline_train_step"):
@@ -143,9 +143,9 @@ def rocprof_table(tag, name, what):
 def generate(tag):
     lines = [BEGIN.format(tag=tag), ""]
     lines += bench_tables(tag)
-    lines += rocprof_table(tag, "kernel_stats_headline.txt", "`python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-gemm-tuning "
+    lines += rocprof_table(tag, "kernel_stats_headline.txt", "`python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-gemm-tuning "
                            "--headline-only` (only the launches `roofline.avg_launch_us` averages: calibrated frames + hot-path passes)")
-    lines += rocprof_table(tag, "kernel_stats.txt", "`python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-gemm-tuning` (the forward "
+    lines += rocprof_table(tag, "kernel_stats.txt", "`python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-gemm-tuning` (the forward "
                            "kernel's row mixes six inputs here: calibrated, init weights, uncalibrated, the spread sweep, iid, training)")
     lines += microbench_tables(tag)
     lines += rocprof_table(tag, "microbench_kernel_stats.txt", "`python tools/microbench.py --iters 10` (realistic AND uniform inputs: "

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/profile_$TAG; mkdir -p $O; cd $R
 # profiles/*_traffic.json; the copy into profiles/ here is in the box's scratch checkout -- commit it from gpurun_out/)
 bash tools/profile_bench.sh $TAG > $O/profile_bench.log 2>&1
 cp $O/${TAG}_traffic.json $R/profiles/ 2>/dev/null
-python bench.py 2> $O/bench_stderr.log | tail -1 > $O/${TAG}_bench.json
+python bench.py --full 2> $O/bench_stderr.log | tail -1 > $O/${TAG}_bench.json
 cat $O/${TAG}_bench.json
 (python tools/microbench.py --iters 30; python tools/microbench.py --iters 10 --config multiviewx; python tools/microbench.py --iters 5 --config stress16) 2>&1 | grep -v amdgpu.ids > $O/${TAG}_microbench.txt
 cd /tmp && export TMPDIR=/tmp
