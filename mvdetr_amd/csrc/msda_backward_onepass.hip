@@ -139,6 +139,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::WPS) void msda_bwd_onepass(
     constexpr int CH = NC ? NC : CAMS;                        // cameras per pass of pass 1
     static_assert(NC == 0 || (NC >= 1 && NC <= CAMS), "at most 8 cameras per pass");
     constexpr unsigned MASS_ONE = 1u << 20, MASS_CLAMP = MASS_ONE + 1u;          // guessed-scale jobs: see `guess` below
+    static_assert(CELLS * TILE_MAX_LEVELS * P <= (MASS_ONE >> 8), "a job without mass reads at most one unit per tap (`too_large`)");
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     float *const vwin = reinterpret_cast<float *>(lds_raw);                               // [NSLOT][16]
     long long *const win64 = reinterpret_cast<long long *>(lds_raw + VW);                 // [NSLOT][8]
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::WPS) void msda_bwd_onepass(
             const int64_t level_base = ((int64_t)b * S + lsi[l]) * row;
             // `guess`: the fixed-point scale from the unit's Gmax and twice the previous job's measured weight mass, no bound
             // pass; the job measures its own mass (each add rounded up and clamped to MASS_CLAMP, so that neither a wrap nor a
-            // single huge weight can hide an overflow) and is repeated exactly if that exceeds the guess
+            // single huge weight can hide an overflow) and is repeated exactly if that exceeds the guess or is 2^-4 of it or less
             bool guess = Wprev > 0.f && Wprev < INFINITY && Gmax_u > 0.f && Gmax_u < INFINITY;
             float Wmax = 0.f, scale = 0.f, inv_scale = 0.f, mscale = 0.f;
             [[maybe_unused]] int e_job = 0;                   // the job's fixed point: steps of 2^(e_job - 30)
@@ -830,12 +831,19 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::WPS) void msda_bwd_onepass(
                 float Wm = (float)wm, fbad = bad ? 1.f : 0.f;
                 block_max2(Wm, fbad);                         // (its first barrier: every lane has read the mass array)
                 for (int i = tid_v; i < NSLOT; i += THREADS) mass2[i] = 0u;
-                if (Wm <= (float)MASS_ONE && fbad == 0.f) {
+                // far too LARGE a guess costs bits: every contribution was rounded to steps of the guessed bound, and a job with
+                // 2^-k of the guessed mass keeps ~29 - k of them (a level or head many decades lighter than the job before).  A
+                // kept job measured more than 2^-4 of its guess: its steps are at most ~2^-25 of its own bound (2^-8 was measured
+                // too coarse for 12 levels' sums, tests/test_msda_mass_skew_gpu.py).  (Each add is rounded up, so a job of next to
+                // no mass still reads up to one unit per tap -- at most 64 cells x 16 levels x 4 points = MASS_ONE >> 8 on one
+                // token -- and is caught; a job that put nothing into the window has nothing to lose.)
+                const bool too_large = Wm > 0.f && Wm <= (float)(MASS_ONE >> 4);
+                if (Wm <= (float)MASS_ONE && fbad == 0.f && !too_large) {
                     Wmax = Wm * (1.f + 1e-6f) / mscale;       // what the next level builds its guess on
                     break;
                 }
-                // too small (or a weight that is not finite): once more, exactly.  The window starts from zero again; what pass 1
-                // stored of the sampling gradients did not depend on the scale and is simply written a second time.
+                // too small or far too large (or a weight that is not finite): once more, exactly.  The window starts from zero
+                // again; what pass 1 stored of the sampling gradients did not depend on the scale and is simply written a second time.
                 for (int i = tid_v; i < NSLOT * NPAIR; i += THREADS) win64[i] = 0;
                 guess = false;                                // (pass 0's barriers order the zeroing before the new adds)
                 repeat = true;

@@ -80,6 +80,10 @@ def _warp_case():
 
 
 BWD_CASES = ["bwd_encoder", "bwd_encoder_b2", "bwd_encoder_d32", "bwd_far", "bwd_uniform", "bwd_wildtrack"]
+# skewed attention-weight mass at Wildtrack size (helpers.SKEW_CASES, test_msda_mass_skew_gpu.py): the bwd child runs them too,
+# public ones through ms_deform_attn_backward and the fused one through the fused training pair, which reads the same knob
+# (default / split / atomic: msda_bwd_onepass<fused, DOTS = 0>; twopass: msda_bwd_value_tok<fused>; onepass: msda_bwd_onepass<fused>)
+SKEW_KNOB_CASES = ["level_cliff_wildtrack", "head_cliff_wildtrack", "band_cliff_wildtrack", "fused_level_cliff_wildtrack"]
 FWD_CASES = ["fwd_encoder", "fwd_encoder_d32", "fwd_uniform"]
 
 
@@ -102,6 +106,16 @@ def _child(family, out_path):
                 res = [torch.tensor([lhs, rhs_v, rhs_a], dtype=torch.float64), res[1][:, sub].contiguous(), res[2][:, sub].contiguous(),
                        res[0].double().abs().sum()]
             results[case] = res
+        from helpers import skew_case
+        for case in SKEW_KNOB_CASES:
+            form, x = skew_case(case)
+            if form == "public":
+                value, shapes, lsi, loc, aw, go = [t.cuda() for t in x]
+                results["skew:" + case] = [t.cpu() for t in MSDA.ms_deform_attn_backward(value, shapes, lsi, loc, aw, go, 64)]
+            else:
+                value, shapes, lsi, ref, raw, _, go = [t.cuda() for t in x]
+                out, stats = MSDA.ms_deform_attn_forward_fused_train(value, shapes, lsi, ref, raw)
+                results["skew:" + case] = [t.cpu() for t in MSDA.ms_deform_attn_backward_fused(go, value, shapes, lsi, ref, raw, stats, out)]
     elif family == "fwd":
         for case in FWD_CASES:
             value, shapes, lsi, loc, aw = [x.cuda() for x in _fwd_case(case)]
@@ -127,7 +141,12 @@ def _run_child(family, env):
         with tempfile.TemporaryDirectory() as tmp:
             out = os.path.join(tmp, "out.pt")
             subprocess.run([sys.executable, os.path.abspath(__file__), family, out], env=dict(os.environ, **env), check=True, timeout=900)
-            _CACHE[key] = torch.load(out)
+            res = torch.load(out)
+        # (the skewed cases' gradients are large: kept only as their block bars)
+        from helpers import skew_bars, skew_reference
+        for k in [k for k in res if k.startswith("skew:")]:
+            res[k] = skew_bars(k[5:], res[k], skew_reference(k[5:]))
+        _CACHE[key] = res
     return _CACHE[key]
 
 
@@ -174,6 +193,17 @@ def test_backward_routes_at_wildtrack_size(env):
     _, rl, ra = c_oracle.msda_backward(value.double(), shapes, lsi, lo, awc, goc)
     assert ((gl.double() - rl).abs() / (50 + rl.abs())).max().item() < 1e-4
     assert ((ga.double() - ra).abs() / (1 + ra.abs())).max().item() < 5e-4
+
+
+@pytest.mark.parametrize("env", BWD_ROUTES, ids=_route_id)
+@pytest.mark.parametrize("case", SKEW_KNOB_CASES)
+def test_backward_routes_per_block_under_mass_skew(case, env):
+    """Every backward route -- and the fused training pair under the same knob -- with levels, heads or column bands of queries
+    carrying 2^-4 to 2^-30 of the others' attention-weight mass: the block bars of test_msda_mass_skew_gpu.py (grad_value
+    within 2e-5 of its [b, level, head] block's maximum, the sampling gradients within 2e-4 of theirs)."""
+    sys.path.insert(0, HERE)
+    from helpers import assert_skew_bars
+    assert_skew_bars(case, _run_child("bwd", env)["skew:" + case])
 
 
 @pytest.mark.parametrize("env", FWD_ROUTES, ids=_route_id)

@@ -22,7 +22,7 @@ trace_of() {   # trace_of <filter> <env assignments...> -- <command...>
   python tools/rocpd_summary.py $O/_trace/t_results.db --filter "$filt" | cut -c1-70,112-160; rm -rf $O/_trace
 }
 case $task in
-tests) python -m pytest tests -m gpu -x -q "$@" 2>&1 | tail -8 ;;
+tests) python -m pytest tests -m gpu -x -q "$@" 2>&1 | tail -8; exit ${PIPESTATUS[0]} ;;
 bench)
   ( time python bench.py --full "$@" ) > $O/bench_run.log 2>&1
   grep '^{' $O/bench_run.log | tail -1 > $O/bench_line.json
@@ -59,9 +59,10 @@ pmc)
   ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc "$@" -d $O/_pmc -o p -- python $R/tools/microbench.py --iters 3 > /dev/null 2>&1 )
   python tools/rocpd_summary.py $O/_pmc/p_results.db --filter mvdetr | cut -c1-200; rm -rf $O/_pmc ;;
 det)
-  python -m pytest tests/test_msda_deterministic_gpu.py -m gpu -x -q 2>&1 | tail -5
+  python -m pytest tests/test_msda_deterministic_gpu.py -m gpu -x -q 2>&1 | tail -5; rc=${PIPESTATUS[0]}
   MVDETR_MSDA_BWD_DETERMINISTIC=1 python tools/microbench.py --only msda --iters 30 2>&1 | grep "msda_bwd"
-  trace_of "msda_" MVDETR_MSDA_BWD_DETERMINISTIC=1 -- python $R/tools/microbench.py --only msda --iters 10 ;;
+  trace_of "msda_" MVDETR_MSDA_BWD_DETERMINISTIC=1 -- python $R/tools/microbench.py --only msda --iters 10
+  exit $rc ;;
 soak)
   python tools/fuzz_parity.py --minutes ${1:-8} --seed ${2:-11} 2>&1 | grep -v amdgpu.ids | tail -12
   python tools/fuzz_warp.py --minutes ${3:-3} --seed ${2:-11} 2>&1 | grep -v amdgpu.ids | tail -6 ;;
