@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 14   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic */
+#define MVDETR_OPS_ABI_VERSION 15   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_* */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -319,6 +319,44 @@ int mvdetr_msda_release_scratch(void);
 int mvdetr_transpose_f32(void *stream, const float *src, int n, int rows, int cols, float *dst);
 int mvdetr_transpose_f64(void *stream, const double *src, int n, int rows, int cols, double *dst);
 
+/* ---- Deformable convolution (ABI 15) ------------------------------------------------------------------------------
+ * torchvision.ops.deform_conv2d v1 (no modulation mask, weight groups 1) -- the DeformConv2d of the reference's
+ * DeformConvWorldFeat (conv_world_feat.py:55-76).
+ *   input  [batch, in_channels, in_h, in_w]: NCHW, or channel-last memory ([batch, in_h, in_w, in_channels]) when
+ *          input_nhwc != 0; grad_input has the same layout
+ *   offset [batch, 2 * offset_groups * kernel_h * kernel_w, out_h, out_w]; channel 2 (g kh kw + i kw + j) is dy of group g,
+ *          tap (i, j), the next one dx; group g owns in_channels / offset_groups input channels
+ *   weight [out_channels, in_channels, kernel_h, kernel_w], bias [out_channels] or NULL; out [batch, out_channels, out_h, out_w]
+ *   out_h = (in_h + 2 pad_h - dil_h (kernel_h - 1) - 1) / stride_h + 1 (out_w likewise): F.conv2d's output size
+ * Sample of tap (i, j): bilinear at y = h stride_h - pad_h + i dil_h + dy, x likewise, in pixel units (no -0.5 shift); 0
+ * when y <= -1, y >= in_h, x <= -1 or x >= in_w; corners outside the image contribute 0.
+ * Backward: grad_input is ACCUMULATED into (pass it zeroed); grad_offset and grad_weight are written.  The offset gradient
+ * is the derivative of the bilinear weights with the floor held fixed.  grad_bias is grad_out summed over (batch, h, w): not
+ * computed here.  Results are not bit-reproducible run to run (atomics).
+ * fp32 calls with a channel-last input, offset_groups 1, in_channels % 16 == 0, out_channels % 32 == 0 and a 16-byte aligned
+ * input run the MFMA implicit-GEMM kernels ("dc_fwd_mfma" / "dc_bwd_mfma"); every other call the generic kernels
+ * ("dc_fwd_generic" / "dc_bwd_generic").  Return 0, hipErrorInvalidValue or the launch's HIP error. */
+int mvdetr_deform_conv2d_forward_f32(void *stream, const float *input, const float *offset, const float *weight,
+                                     const float *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                     int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                     int dil_w, int offset_groups, int input_nhwc, float *out);
+int mvdetr_deform_conv2d_forward_f64(void *stream, const double *input, const double *offset, const double *weight,
+                                     const double *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                     int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                     int dil_w, int offset_groups, int input_nhwc, double *out);
+int mvdetr_deform_conv2d_backward_f32(void *stream, const float *grad_out, const float *input, const float *offset,
+                                      const float *weight, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                      int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                      int dil_w, int offset_groups, int input_nhwc, float *grad_input, float *grad_offset,
+                                      float *grad_weight);
+int mvdetr_deform_conv2d_backward_f64(void *stream, const double *grad_out, const double *input, const double *offset,
+                                      const double *weight, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                      int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                      int dil_w, int offset_groups, int input_nhwc, double *grad_input, double *grad_offset,
+                                      double *grad_weight);
+/* Name of the kernel route the last deformable-convolution call of this process took (any thread). Static; never NULL. */
+const char *mvdetr_deform_conv2d_last_kernel(void);
+
 /* ---- CPU path (host pointers, no stream, synchronous) ------------------------------------------------------------
  * The reference extension raises for CPU tensors (ms_deform_attn_cpu.cpp:17-41 are stubs; ms_deform_attn.h:38,60).
  * These entry points make the same contracts work on host memory: same argument meaning and layouts as the device
@@ -347,6 +385,27 @@ int mvdetr_warp_perspective_backward_host_f32(const float *grad_dst, const float
                                               int src_w, int dst_h, int dst_w, int layout_nhwc, int mode, float *grad_src);
 int mvdetr_warp_perspective_backward_host_f64(const double *grad_dst, const double *mats, int n, int channels, int src_h,
                                               int src_w, int dst_h, int dst_w, int layout_nhwc, int mode, double *grad_src);
+
+/* deformable convolution on host memory: same arguments as the device entries without the stream; grad_input is
+ * accumulated into, grad_offset and grad_weight are written; deterministic */
+int mvdetr_deform_conv2d_forward_host_f32(const float *input, const float *offset, const float *weight, const float *bias,
+                                          int batch, int in_channels, int in_h, int in_w, int out_channels, int kernel_h,
+                                          int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                          int offset_groups, int input_nhwc, float *out);
+int mvdetr_deform_conv2d_forward_host_f64(const double *input, const double *offset, const double *weight, const double *bias,
+                                          int batch, int in_channels, int in_h, int in_w, int out_channels, int kernel_h,
+                                          int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                          int offset_groups, int input_nhwc, double *out);
+int mvdetr_deform_conv2d_backward_host_f32(const float *grad_out, const float *input, const float *offset, const float *weight,
+                                           int batch, int in_channels, int in_h, int in_w, int out_channels, int kernel_h,
+                                           int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                           int offset_groups, int input_nhwc, float *grad_input, float *grad_offset,
+                                           float *grad_weight);
+int mvdetr_deform_conv2d_backward_host_f64(const double *grad_out, const double *input, const double *offset,
+                                           const double *weight, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                           int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
+                                           int dil_h, int dil_w, int offset_groups, int input_nhwc, double *grad_input,
+                                           double *grad_offset, double *grad_weight);
 
 #ifdef __cplusplus
 }

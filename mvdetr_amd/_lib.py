@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # MVDETR_OPS_LIB: another build of the same sources (the phase-stamp build libmvdetr_ops_trace.so of tools/experiments)
 LIB_PATH = os.environ.get("MVDETR_OPS_LIB") or os.path.join(CSRC, "libmvdetr_ops.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _vp, _i = ctypes.c_void_p, ctypes.c_int
 _MSDA_FWD = [_vp] * 6 + [_i] * 7 + [_vp]
@@ -28,6 +28,8 @@ _MSDA_BWD_HOST = [_vp] * 6 + [_i] * 7 + [_vp] * 3
 _WARP_HOST = [_vp] * 2 + [_i] * 8 + [_vp]
 _MSDA_FUSED = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 10 + [_vp]
 _MSDA_FUSED_LEVELS = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 12 + [_vp]
+_DC_FWD = [_vp] * 5 + [_i] * 15 + [_vp]
+_DC_BWD = [_vp] * 5 + [_i] * 15 + [_vp] * 3
 
 SIGNATURES = {
     "mvdetr_ops_abi_version": ([], _i),
@@ -76,6 +78,15 @@ SIGNATURES = {
     "mvdetr_warp_perspective_forward_host_f64": (_WARP_HOST, _i),
     "mvdetr_warp_perspective_backward_host_f32": (_WARP_HOST, _i),
     "mvdetr_warp_perspective_backward_host_f64": (_WARP_HOST, _i),
+    "mvdetr_deform_conv2d_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_deform_conv2d_forward_f32": (_DC_FWD, _i),
+    "mvdetr_deform_conv2d_forward_f64": (_DC_FWD, _i),
+    "mvdetr_deform_conv2d_backward_f32": (_DC_BWD, _i),
+    "mvdetr_deform_conv2d_backward_f64": (_DC_BWD, _i),
+    "mvdetr_deform_conv2d_forward_host_f32": (_DC_FWD[1:], _i),
+    "mvdetr_deform_conv2d_forward_host_f64": (_DC_FWD[1:], _i),
+    "mvdetr_deform_conv2d_backward_host_f32": (_DC_BWD[1:], _i),
+    "mvdetr_deform_conv2d_backward_host_f64": (_DC_BWD[1:], _i),
 }
 
 

@@ -13,6 +13,9 @@
 //   forward   threads own contiguous ranges of (batch, query);
 //   backward  threads own (batch, head) pairs: grad_value[b, :, m, :] is then written by exactly one thread;
 //   warp      forward: threads own destination rows; backward: threads own (view, channel) planes of grad_src.
+//   deform_conv  (torchvision.ops.deform_conv2d v1) per batch item and 1024-pixel chunk: the column matrix col[p][c kh kw + tap]
+//             and its gradient g_col are formed with threads owning pixels; grad_weight with threads owning output channels,
+//             grad_input with threads owning input channels.
 #include "../../include/mvdetr_ops.h"
 
 #include <algorithm>
@@ -271,6 +274,173 @@ int warp_host(const T *src_or_gdst, const T *mats, int n, int C, int sh, int sw,
     return 0;
 }
 
+// ---- deformable convolution ----------------------------------------------------------------------------------------------
+
+struct DcDims {
+    int B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G, nhwc;
+};
+
+bool dc_dims(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, int nhwc,
+             DcDims &d)
+{
+    if (B < 0 || C < 0 || H < 1 || W < 1 || Co < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
+        dw < 1 || G < 1 || C % G != 0)
+        return false;
+    const int eh = H + 2 * ph - dh * (kh - 1) - 1, ew = W + 2 * pw - dw * (kw - 1) - 1;
+    if (eh < 0 || ew < 0) return false;
+    d = DcDims{B, C, H, W, Co, eh / sh + 1, ew / sw + 1, kh, kw, sh, sw, ph, pw, dh, dw, G, nhwc ? 1 : 0};
+    return true;
+}
+
+// footprint of output pixel p, group g, tap: corner element offsets (channel 0 of batch item 0), weights, validity
+template <typename T> struct DcTap {
+    int64_t at[4];
+    T w[4];
+    bool ok[4];
+    bool in;
+    T ly, lx;
+};
+
+template <typename T> DcTap<T> dc_tap(const DcDims &d, const T *off, int b, int g, int tap, int p)
+{
+    const int T_ = d.kh * d.kw, HWo = d.Ho * d.Wo;
+    const int ho = p / d.Wo, wo = p % d.Wo, i = tap / d.kw, j = tap % d.kw;
+    const T *o = off + ((int64_t)b * 2 * d.G * T_ + 2 * (g * T_ + tap)) * HWo + p;
+    const T y = T(ho * d.sh - d.ph + i * d.dh) + o[0], x = T(wo * d.sw - d.pw + j * d.dw) + o[HWo];
+    DcTap<T> t;
+    t.in = y > T(-1) && y < T(d.H) && x > T(-1) && x < T(d.W);
+    const T fy = t.in ? std::floor(y) : T(0), fx = t.in ? std::floor(x) : T(0);
+    const int y0 = (int)fy, x0 = (int)fx;
+    t.ly = t.in ? y - fy : T(0);
+    t.lx = t.in ? x - fx : T(0);
+    const int ys[4] = {y0, y0, y0 + 1, y0 + 1}, xs[4] = {x0, x0 + 1, x0, x0 + 1};
+    const T wy[4] = {1 - t.ly, 1 - t.ly, t.ly, t.ly}, wx[4] = {1 - t.lx, t.lx, 1 - t.lx, t.lx};
+    const int64_t pst = d.nhwc ? d.C : 1;
+    for (int k = 0; k < 4; ++k) {
+        t.ok[k] = t.in && ys[k] >= 0 && ys[k] < d.H && xs[k] >= 0 && xs[k] < d.W;
+        t.at[k] = t.ok[k] ? ((int64_t)ys[k] * d.W + xs[k]) * pst : 0;
+        t.w[k] = wy[k] * wx[k];
+    }
+    return t;
+}
+
+constexpr int DC_CHUNK = 1024;
+
+// col[pl][c * T + tap] for the pixels [p0, p0 + np) of batch item b
+template <typename T> void dc_columns(const DcDims &d, const T *in, const T *off, int b, int p0, int np, T *col)
+{
+    const int T_ = d.kh * d.kw, Cg = d.C / d.G, K = d.C * T_;
+    const int64_t HW = (int64_t)d.H * d.W, cst = d.nhwc ? 1 : HW;
+    const T *inb = in + (int64_t)b * d.C * HW;
+    parallel_ranges(np, [&](int64_t a, int64_t e) {
+        for (int64_t pl = a; pl < e; ++pl) {
+            T *row = col + pl * K;
+            for (int g = 0; g < d.G; ++g)
+                for (int tap = 0; tap < T_; ++tap) {
+                    const DcTap<T> t = dc_tap(d, off, b, g, tap, p0 + (int)pl);
+                    for (int c = g * Cg; c < (g + 1) * Cg; ++c) {
+                        T v = T(0);
+                        for (int k = 0; k < 4; ++k)
+                            if (t.ok[k]) v += t.w[k] * inb[c * cst + t.at[k]];
+                        row[c * T_ + tap] = v;
+                    }
+                }
+        }
+    });
+}
+
+template <typename T>
+int dc_forward_host(const T *in, const T *off, const T *wt, const T *bias, const DcDims &d, T *out)
+{
+    const int K = d.C * d.kh * d.kw, HWo = d.Ho * d.Wo;
+    std::vector<T> col((size_t)DC_CHUNK * K);
+    for (int b = 0; b < d.B; ++b)
+        for (int p0 = 0; p0 < HWo; p0 += DC_CHUNK) {
+            const int np = std::min(DC_CHUNK, HWo - p0);
+            dc_columns(d, in, off, b, p0, np, col.data());
+            parallel_ranges(np, [&](int64_t a, int64_t e) {
+                for (int64_t pl = a; pl < e; ++pl) {
+                    const T *row = col.data() + pl * K;
+                    for (int o = 0; o < d.Co; ++o) {
+                        const T *w = wt + (int64_t)o * K;
+                        T acc = bias ? bias[o] : T(0);
+                        for (int k = 0; k < K; ++k) acc += w[k] * row[k];
+                        out[((int64_t)b * d.Co + o) * HWo + p0 + pl] = acc;
+                    }
+                }
+            });
+        }
+    return 0;
+}
+
+template <typename T>
+int dc_backward_host(const T *gout, const T *in, const T *off, const T *wt, const DcDims &d, T *gin, T *goff, T *gw)
+{
+    const int T_ = d.kh * d.kw, K = d.C * T_, HWo = d.Ho * d.Wo, Cg = d.C / d.G;
+    const int64_t HW = (int64_t)d.H * d.W, cst = d.nhwc ? 1 : HW;
+    std::fill(gw, gw + (int64_t)d.Co * K, T(0));
+    std::vector<T> col((size_t)DC_CHUNK * K), gcol((size_t)DC_CHUNK * K);
+    for (int b = 0; b < d.B; ++b)
+        for (int p0 = 0; p0 < HWo; p0 += DC_CHUNK) {
+            const int np = std::min(DC_CHUNK, HWo - p0);
+            const T *gob = gout + (int64_t)b * d.Co * HWo + p0;
+            dc_columns(d, in, off, b, p0, np, col.data());
+            parallel_ranges(d.Co, [&](int64_t a, int64_t e) {                  // grad_weight: threads own output channels
+                for (int64_t o = a; o < e; ++o) {
+                    T *w = gw + o * K;
+                    for (int pl = 0; pl < np; ++pl) {
+                        const T go = gob[o * HWo + pl];
+                        const T *row = col.data() + (int64_t)pl * K;
+                        for (int k = 0; k < K; ++k) w[k] += go * row[k];
+                    }
+                }
+            });
+            parallel_ranges(np, [&](int64_t a, int64_t e) {                    // g_col and grad_offset: threads own pixels
+                for (int64_t pl = a; pl < e; ++pl) {
+                    T *row = gcol.data() + pl * K;
+                    std::fill(row, row + K, T(0));
+                    for (int o = 0; o < d.Co; ++o) {
+                        const T go = gob[(int64_t)o * HWo + pl];
+                        const T *w = wt + (int64_t)o * K;
+                        for (int k = 0; k < K; ++k) row[k] += w[k] * go;
+                    }
+                    const T *inb = in + (int64_t)b * d.C * HW;
+                    for (int g = 0; g < d.G; ++g)
+                        for (int tap = 0; tap < T_; ++tap) {
+                            const DcTap<T> t = dc_tap(d, off, b, g, tap, p0 + (int)pl);
+                            T gy = T(0), gx = T(0);
+                            if (t.in)
+                                for (int c = g * Cg; c < (g + 1) * Cg; ++c) {
+                                    T v[4];
+                                    for (int k = 0; k < 4; ++k) v[k] = t.ok[k] ? inb[c * cst + t.at[k]] : T(0);
+                                    const T gc = row[c * T_ + tap];
+                                    gy += gc * ((1 - t.lx) * (v[2] - v[0]) + t.lx * (v[3] - v[1]));
+                                    gx += gc * ((1 - t.ly) * (v[1] - v[0]) + t.ly * (v[3] - v[2]));
+                                }
+                            T *go_ = goff + ((int64_t)b * 2 * d.G * T_ + 2 * (g * T_ + tap)) * HWo + p0 + pl;
+                            go_[0] = gy;
+                            go_[HWo] = gx;
+                        }
+                }
+            });
+            parallel_ranges(d.C, [&](int64_t a, int64_t e) {                   // grad_input: threads own input channels
+                T *ginb = gin + (int64_t)b * d.C * HW;
+                for (int64_t c = a; c < e; ++c) {
+                    const int g = (int)(c / Cg);
+                    for (int pl = 0; pl < np; ++pl)
+                        for (int tap = 0; tap < T_; ++tap) {
+                            const DcTap<T> t = dc_tap(d, off, b, g, tap, p0 + pl);
+                            if (!t.in) continue;
+                            const T gc = gcol[(int64_t)pl * K + c * T_ + tap];
+                            for (int k = 0; k < 4; ++k)
+                                if (t.ok[k]) ginb[c * cst + t.at[k]] += t.w[k] * gc;
+                        }
+                }
+            });
+        }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,4 +496,43 @@ int mvdetr_warp_perspective_backward_host_f64(const double *grad_dst, const doub
     return warp_host<double, true>(grad_dst, mats, n, channels, src_h, src_w, dst_h, dst_w, layout_nhwc, mode, grad_src);
 }
 
+#define MVDETR_DC_HOST_ENTRIES(T, SFX)                                                                                        \
+    int mvdetr_deform_conv2d_forward_host_##SFX(const T *input, const T *offset, const T *weight, const T *bias, int batch,   \
+                                                int in_channels, int in_h, int in_w, int out_channels, int kernel_h,         \
+                                                int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,   \
+                                                int dil_w, int offset_groups, int input_nhwc, T *out)                        \
+    {                                                                                                                         \
+        DcDims d;                                                                                                             \
+        if (!dc_dims(batch, in_channels, in_h, in_w, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,      \
+                     dil_h, dil_w, offset_groups, input_nhwc, d))                                                             \
+            return 1;                                                                                                         \
+        if ((int64_t)d.B * d.Co * d.Ho * d.Wo == 0) return 0;                                                                 \
+        if (!out || !offset || (d.C && (!input || !weight))) return 1;                                                        \
+        return dc_forward_host<T>(input, offset, weight, bias, d, out);                                                       \
+    }                                                                                                                         \
+    int mvdetr_deform_conv2d_backward_host_##SFX(const T *grad_out, const T *input, const T *offset, const T *weight,         \
+                                                 int batch, int in_channels, int in_h, int in_w, int out_channels,            \
+                                                 int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, \
+                                                 int dil_h, int dil_w, int offset_groups, int input_nhwc, T *grad_input,      \
+                                                 T *grad_offset, T *grad_weight)                                              \
+    {                                                                                                                         \
+        DcDims d;                                                                                                             \
+        if (!dc_dims(batch, in_channels, in_h, in_w, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,      \
+                     dil_h, dil_w, offset_groups, input_nhwc, d))                                                             \
+            return 1;                                                                                                         \
+        const int64_t np = (int64_t)d.B * d.Ho * d.Wo, nw = (int64_t)d.Co * d.C * d.kh * d.kw;                               \
+        if ((np && (!grad_offset || !offset)) || (nw && !grad_weight)) return 1;                                              \
+        if (np * d.Co * d.C != 0 && (!grad_out || !input || !weight || !grad_input)) return 1;                                     \
+        if (np * d.Co * d.C == 0) {                                                                                           \
+            if (np) std::fill(grad_offset, grad_offset + np * 2 * d.G * d.kh * d.kw, T(0));                                  \
+            if (nw) std::fill(grad_weight, grad_weight + nw, T(0));                                                           \
+            return 0;                                                                                                         \
+        }                                                                                                                     \
+        return dc_backward_host<T>(grad_out, input, offset, weight, d, grad_input, grad_offset, grad_weight);                 \
+    }
+
+MVDETR_DC_HOST_ENTRIES(float, f32)
+MVDETR_DC_HOST_ENTRIES(double, f64)
+
 }  // extern "C"
+

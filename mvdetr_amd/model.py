@@ -17,7 +17,7 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
-from .world_feat import ConvWorldFeat, DeformTransWorldFeat
+from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat
 
 
 class BasicBlock(nn.Module):
@@ -175,8 +175,11 @@ class MVDeTr(nn.Module):
                                                    n_points=n_points, stride=2, reference_points=ref)
         elif world_feat_arch == "conv":
             self.world_feat = ConvWorldFeat(geom.num_cam, geom.Rworld_shape, base_dim, hidden_dim=base_dim)
+        elif world_feat_arch == "deform_conv":
+            # the world heads take base_dim channels (mvdetr.py:139-140): the reference's default hidden_dim=128 is base_dim
+            self.world_feat = DeformConvWorldFeat(geom.num_cam, geom.Rworld_shape, base_dim, hidden_dim=base_dim)
         else:
-            raise ValueError("world_feat_arch must be 'deform_trans' or 'conv'")
+            raise ValueError("world_feat_arch must be 'deform_trans', 'conv' or 'deform_conv'")
         self.world_heatmap = output_head(base_dim, outfeat_dim, 1)
         self.world_offset = output_head(base_dim, outfeat_dim, 2)
         # init (mvdetr.py:142-148)
@@ -235,7 +238,7 @@ class MVDeTr(nn.Module):
         imgs_heatmap, imgs_offset, imgs_wh = self.img_heatmap(feat), self.img_offset(feat), self.img_wh(feat)
         H, W = self.Rworld_shape
         C = feat.shape[1]
-        nhwc = self.channels_last and self.world_feat_arch == "deform_trans"
+        nhwc = self.channels_last and self.world_feat_arch in ("deform_trans", "deform_conv")
         world = warp_perspective(feat, proj, (H, W), channels_last_out=nhwc)
         world = world.view(B, N, H, W, C) if nhwc else world.view(B, N, C, H, W)
         world = self.world_feat(world)
@@ -246,7 +249,7 @@ class MVDeTr(nn.Module):
         H, W = self.Rworld_shape
         N = self.num_cam
         B = feat.shape[0] // N
-        nhwc = self.channels_last and self.world_feat_arch == "deform_trans"
+        nhwc = self.channels_last and self.world_feat_arch in ("deform_trans", "deform_conv")
         world = warp_perspective(feat, proj, (H, W), channels_last_out=nhwc)
         world = world.view(B, N, H, W, -1) if nhwc else world.view(B, N, -1, H, W)
         return self.world_feat(world)

@@ -1,0 +1,196 @@
+"""deform_conv2d / DeformConv2d: torchvision.ops' deformable convolution (v1) on the library's own kernels.
+
+The reference's ``deform_conv`` ground-plane aggregator (multiview_detector/models/conv_world_feat.py:5,55-76) takes
+``torchvision.ops.DeformConv2d``, a compiled CUDA op.  These have torchvision's signatures and results:
+
+* ``deform_conv2d(input, offset, weight, bias=None, stride=1, padding=0, dilation=1, mask=None)``
+* ``DeformConv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True)``
+
+Sampling: tap (i, j) of output pixel (h, w) reads the input bilinearly at y = h * stride - padding + i * dilation + dy
+(x likewise) in pixel units, 0 outside (-1, H) x (-1, W); offset channel 2 (g * kh * kw + i * kw + j) is dy of offset group
+g, the next one dx (include/mvdetr_ops.h).  CUDA tensors run the HIP kernels of csrc/deform_conv.hip -- fp32 with a
+channel-last input (``torch.channels_last``, e.g. ``warp_perspective(..., channels_last_out=True)`` viewed as NCHW), one
+offset group, C_in % 16 == 0 and C_out % 32 == 0 take the MFMA implicit GEMM; an NCHW input of that shape is transposed to
+channel-last first; everything else takes the generic kernels.  CPU tensors run the library's host path.  Gradients flow to
+input, offset, weight and bias; the backward is not bit-reproducible run to run (atomics), like torchvision's CUDA kernel.
+Not provided: the DCNv2 modulation ``mask`` and weight ``groups > 1`` (NotImplementedError), 16-bit dtypes (RuntimeError).
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+from torch.nn.modules.utils import _pair
+
+from .. import _lib
+from .warp import _transpose
+
+
+def last_kernel() -> str:
+    """Route of the last deformable-convolution call of this process on the device: "dc_fwd_mfma", "dc_fwd_generic",
+    "dc_bwd_mfma" or "dc_bwd_generic" (tests / tools introspection)."""
+    return _lib.lib().mvdetr_deform_conv2d_last_kernel().decode()
+
+
+def _fast_shape(x, weight, offset_groups):
+    B, C, H, W = x.shape
+    return (x.is_cuda and x.dtype == torch.float32 and offset_groups == 1 and C % 16 == 0 and C > 0
+            and weight.shape[0] % 32 == 0 and weight.shape[0] > 0 and B <= 65535 and (H * W + 63) // 64 <= 65535)
+
+
+def _layout(x, weight, offset_groups):
+    """(tensor whose memory the kernels read, nhwc flag): a channel-last input is read in place; an NCHW fp32 input of the
+    MFMA kernels' shape is transposed to channel-last by the library's tiled transpose; anything else is read as NCHW."""
+    B, C, H, W = x.shape
+    if x.is_contiguous():
+        if _fast_shape(x, weight, offset_groups) and C > 1 and H * W > 1:
+            t = _transpose(x, B, C, H * W)                                  # memory [B, H*W, C]
+            return t.view(B, H, W, C).permute(0, 3, 1, 2), 1
+        return x, 0
+    if x.is_contiguous(memory_format=torch.channels_last):
+        return x, 1
+    return x.contiguous(), 0
+
+
+def _args(x, weight, conf):
+    (sh, sw), (ph, pw), (dh, dw), G = conf
+    B, C, H, W = x.shape
+    return [B, C, H, W, weight.shape[0], weight.shape[2], weight.shape[3], sh, sw, ph, pw, dh, dw, G]
+
+
+class DeformConv2dFunction(Function):
+    @staticmethod
+    def forward(ctx, input, offset, weight, bias, stride, padding, dilation, offset_groups):
+        conf = (stride, padding, dilation, offset_groups)
+        x, nhwc = _layout(input, weight, offset_groups)
+        offset, weight = offset.contiguous(), weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        B, Co = x.shape[0], weight.shape[0]
+        out = torch.empty((B, Co, offset.shape[2], offset.shape[3]), dtype=x.dtype, device=x.device)
+        sfx = _lib.suffix(x.dtype)
+        args = _args(x, weight, conf) + [nhwc, out.data_ptr()]
+        bias_ptr = None if bias is None else bias.data_ptr()
+        if x.is_cuda:
+            with torch.cuda.device(x.device):
+                rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_forward_{sfx}")(
+                    _lib.current_stream_ptr(x.device), x.data_ptr(), offset.data_ptr(), weight.data_ptr(), bias_ptr, *args)
+        else:
+            rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_forward_host_{sfx}")(
+                x.data_ptr(), offset.data_ptr(), weight.data_ptr(), bias_ptr, *args)
+        _lib.check(rc, "deform_conv2d_forward")
+        ctx.save_for_backward(x, offset, weight)
+        ctx.conf, ctx.nhwc, ctx.has_bias = conf, nhwc, bias is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, offset, weight = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        # grad_input in the layout the kernels read (channel-last memory for a channel-last or transposed input)
+        grad_input = torch.zeros_like(x, memory_format=torch.channels_last if ctx.nhwc else torch.contiguous_format)
+        grad_offset = torch.empty_like(offset)
+        grad_weight = torch.empty_like(weight)
+        sfx = _lib.suffix(x.dtype)
+        args = _args(x, weight, ctx.conf) + [ctx.nhwc, grad_input.data_ptr(), grad_offset.data_ptr(), grad_weight.data_ptr()]
+        if x.is_cuda:
+            with torch.cuda.device(x.device):
+                rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_backward_{sfx}")(
+                    _lib.current_stream_ptr(x.device), grad_out.data_ptr(), x.data_ptr(), offset.data_ptr(),
+                    weight.data_ptr(), *args)
+        else:
+            rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_backward_host_{sfx}")(
+                grad_out.data_ptr(), x.data_ptr(), offset.data_ptr(), weight.data_ptr(), *args)
+        _lib.check(rc, "deform_conv2d_backward")
+        grad_bias = grad_out.sum((0, 2, 3)) if ctx.has_bias else None
+        return grad_input, grad_offset, grad_weight, grad_bias, None, None, None, None
+
+
+def deform_conv2d(input, offset, weight, bias=None, stride=1, padding=0, dilation=1, mask=None):
+    """torchvision.ops.deform_conv2d (v1): input [B, C_in, H, W], offset [B, 2 * G * kh * kw, H_out, W_out], weight
+    [C_out, C_in, kh, kw], bias [C_out] or None -> [B, C_out, H_out, W_out]."""
+    if mask is not None:
+        raise NotImplementedError("deform_conv2d: the DCNv2 modulation mask is not implemented")
+    if input.dim() != 4 or offset.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"deform_conv2d: expected 4-D input, offset and weight, got {tuple(input.shape)}, "
+                         f"{tuple(offset.shape)} and {tuple(weight.shape)}")
+    devices = {t.device for t in (input, offset, weight, bias) if t is not None}
+    if len(devices) != 1:
+        raise RuntimeError(f"deform_conv2d: all tensors must be on one device, got {sorted(map(str, devices))}")
+    dtypes = {t.dtype for t in (input, offset, weight, bias) if t is not None}
+    if len(dtypes) != 1:
+        raise RuntimeError(f"deform_conv2d: all tensors must have one dtype, got {sorted(map(str, dtypes))}")
+    _lib.suffix(input.dtype)                                       # 16-bit dtypes raise here
+    stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
+    B, C, H, W = input.shape
+    Co, Cw, kh, kw = weight.shape
+    if Cw != C:
+        if Cw > 0 and C % Cw == 0:
+            raise NotImplementedError("deform_conv2d: weight groups > 1 are not implemented")
+        raise ValueError(f"deform_conv2d: weight {tuple(weight.shape)} does not fit {C} input channels")
+    if min(stride) < 1 or min(dilation) < 1 or min(padding) < 0:
+        raise ValueError(f"deform_conv2d: stride {stride} and dilation {dilation} must be >= 1, padding {padding} >= 0")
+    if bias is not None and tuple(bias.shape) != (Co,):
+        raise ValueError(f"deform_conv2d: bias {tuple(bias.shape)} does not fit {Co} output channels")
+    if offset.shape[1] % (2 * kh * kw) != 0 or offset.shape[1] == 0:
+        raise RuntimeError(f"the shape of the offset tensor at dimension 1 is not valid. It should be a multiple of "
+                           f"2 * weight.size[2] * weight.size[3].\nGot offset.shape[1]={offset.shape[1]}, while "
+                           f"2 * weight.size[2] * weight.size[3]={2 * kh * kw}")
+    G = offset.shape[1] // (2 * kh * kw)
+    if C % G != 0:
+        raise RuntimeError(f"deform_conv2d: {C} input channels are not a multiple of the {G} offset groups")
+    if offset.shape[0] != B:
+        raise RuntimeError(f"invalid batch size of offset: {offset.shape[0]} for input batch {B}")
+    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
+    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
+    if Ho < 1 or Wo < 1:
+        raise RuntimeError(f"deform_conv2d: calculated output size {Ho}x{Wo} is too small")
+    if tuple(offset.shape[2:]) != (Ho, Wo):
+        raise RuntimeError(f"offset output dims: ({offset.shape[2]}, {offset.shape[3]}) - computed output dims: ({Ho}, {Wo})")
+    return DeformConv2dFunction.apply(input, offset, weight, bias, stride, padding, dilation, G)
+
+
+class DeformConv2d(nn.Module):
+    """torchvision.ops.DeformConv2d: ``forward(input, offset, mask=None)``; parameters ``weight`` [C_out, C_in, kh, kw] and
+    ``bias`` [C_out], initialised as torchvision does (kaiming-uniform with a = sqrt(5), bias uniform in +-1/sqrt(fan_in))."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        super().__init__()
+        if in_channels % groups != 0:
+            raise ValueError("in_channels must be divisible by groups")
+        if out_channels % groups != 0:
+            raise ValueError("out_channels must be divisible by groups")
+        if groups != 1:
+            raise NotImplementedError("DeformConv2d: weight groups > 1 are not implemented")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride = _pair(kernel_size), _pair(stride)
+        self.padding, self.dilation = _pair(padding), _pair(dilation)
+        self.groups = groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, *self.kernel_size))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in, _ = nn.init._calculate_fan_in_and_fan_out(self.weight)
+            bound = 1 / math.sqrt(fan_in)
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, input, offset, mask=None):
+        return deform_conv2d(input, offset, self.weight, self.bias, stride=self.stride, padding=self.padding,
+                             dilation=self.dilation, mask=mask)
+
+    def extra_repr(self) -> str:
+        s = f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}"
+        s += f", padding={self.padding}" if self.padding != (0, 0) else ""
+        s += f", dilation={self.dilation}" if self.dilation != (1, 1) else ""
+        s += f", groups={self.groups}" if self.groups != 1 else ""
+        s += ", bias=False" if self.bias is None else ""
+        return s

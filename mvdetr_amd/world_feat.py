@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .ops.add_layernorm import add_layer_norm, fused_add_layer_norm_available
+from .ops.deform_conv import DeformConv2d
 from .ops.modules import MSDeformAttn
 
 
@@ -241,3 +242,35 @@ class ConvWorldFeat(nn.Module):
         h, w = x.shape[-2:]
         x = torch.cat([x.reshape(B, N * C, h, w), self.coord_map.expand(B, -1, -1, -1)], 1)
         return self.upsample(self.world_feat(x))
+
+
+class DeformConvWorldFeat(nn.Module):
+    """The reference's ``--world_feat deform_conv`` aggregator (multiview_detector/models/conv_world_feat.py:55-76, same
+    submodule names): per camera, the sine position embedding is added, a 1x1 conv predicts the 18 offset channels and a
+    3x3 deformable convolution (ops.DeformConv2d, the HIP kernels of csrc/deform_conv.hip) + ReLU runs; the cameras are
+    concatenated and merged by a 1x1 conv and three dilated 3x3 convs.  The position embedding is a non-persistent buffer
+    (the reference keeps it as a plain attribute), so a reference checkpoint loads with strict=True.
+
+    The input may arrive channel-last ([B, N, H, W, C], straight from warp_perspective(..., channels_last_out=True)): each
+    camera's features are then read in place by the deformable convolution's channel-last kernel."""
+
+    def __init__(self, num_cam, Rworld_shape, base_dim, hidden_dim=128):
+        super().__init__()
+        self.num_cam, self.base_dim = num_cam, base_dim
+        self.register_buffer("pos_embedding", create_pos_embedding(Rworld_shape, base_dim // 2), persistent=False)
+        self.deform_pos = nn.ModuleList([nn.Conv2d(base_dim, 9 * 2, 1) for _ in range(num_cam)])
+        self.deform_conv = nn.ModuleList([DeformConv2d(base_dim, base_dim, 3, padding=1) for _ in range(num_cam)])
+        self.merge_linear = nn.Sequential(nn.Conv2d(base_dim * num_cam, hidden_dim, 1), nn.ReLU())
+        self.world_feat = nn.Sequential(nn.Conv2d(hidden_dim, hidden_dim, 3, padding=1), nn.ReLU(),
+                                        nn.Conv2d(hidden_dim, hidden_dim, 3, padding=2, dilation=2), nn.ReLU(),
+                                        nn.Conv2d(hidden_dim, hidden_dim, 3, padding=4, dilation=4), nn.ReLU())
+
+    def forward(self, x, visualize=False):
+        channel_last = x.shape[2] != self.base_dim                    # [B, N, H, W, C]
+        feats = []
+        for n in range(x.shape[1]):
+            view = x[:, n].permute(0, 3, 1, 2) if channel_last else x[:, n]     # NCHW view (channel-last memory)
+            feat = view + self.pos_embedding
+            pos = self.deform_pos[n](feat)
+            feats.append(F.relu(self.deform_conv[n](feat, pos)))
+        return self.world_feat(self.merge_linear(torch.cat(feats, dim=1)))
