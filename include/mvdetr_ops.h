@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 15   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_* */
+#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_* */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -357,6 +357,45 @@ int mvdetr_deform_conv2d_backward_f64(void *stream, const double *grad_out, cons
 /* Name of the kernel route the last deformable-convolution call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_deform_conv2d_last_kernel(void);
 
+/* ---- Fused multi-head attention (the op inside nn.MultiheadAttention; reference call sites models/transformer.py:40,59) ---
+ *   out[b, h, i, :] = sum_j softmax_j(scale * q[b, h, i, :] . k[b, h, j, :]) * v[b, h, j, :],   scale = 1 / sqrt(head_dim)
+ * for `sq` queries and `sk` >= 1 keys of `batch` x `heads` independent problems; no masks.  No score or probability is
+ * written to memory.  q, k, v, out and the gradients are addressed as  base + b * S[0] + h * S[1] + token * S[2] + channel
+ * (ELEMENT strides; the channel is contiguous), so one [S, B, 3E] in-projection result serves as q, k and v in place.
+ *   strides   HOST pointer (read during the call, an exception to the device-pointer rule): 3 int64 per tensor in the
+ *             order q, k, v, out (forward: 12 values) and q, k, v, out, grad_out, grad_q, grad_k, grad_v (backward: 24).
+ *   lse       [batch, heads, sq] dense: the NATURAL logarithm of sum_j exp(scale * q_i . k_j) (of the SCALED scores);
+ *             written by the forward, read by the backward, which recomputes p_ij = exp(scale * q_i . k_j - lse_i).
+ *   dropout   dropout_p in [0, 1); 0 = none.  Element (b, h, i, j) is KEPT iff
+ *                 hash(seed, ((b * heads + h) * sq + i) * sk + j) >= (uint32_t)(dropout_p * 2^32)
+ *             where hash(seed, idx) is: x = idx * 0x9E3779B97F4A7C15 + seed (mod 2^64); x ^= x >> 30;
+ *             x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31; result = x >> 32
+ *             (csrc/attention_hash.h, the one definition every path includes).  Kept probabilities are multiplied by
+ *             1 / (1 - dropout_p) in the product with v only; lse is that of the undropped probabilities; the backward applies
+ *             the same mask and factor.  Pass the forward's dropout_p and seed to the backward.
+ *   workspace (backward) device buffer of mvdetr_attention_workspace_bytes(...) bytes (delta_i = grad_out_i . out_i).
+ * Every element of out, lse, grad_q, grad_k, grad_v is written; inputs are never written; no atomics: results are
+ * bit-reproducible run to run.  fp32 with head_dim 16 or 32, 16-byte aligned base pointers and strides that are multiples
+ * of 4 take the MFMA kernels ("attn_fwd_mfma" / "attn_bwd_mfma"); everything else with head_dim <= 256 the generic
+ * kernels ("attn_fwd_generic" / "attn_bwd_generic"); head_dim > 256 returns 1. */
+int64_t mvdetr_attention_workspace_bytes(int batch, int heads, int sq, int sk, int head_dim, int elem_size);
+int mvdetr_attention_forward_f32(void *stream, const float *q, const float *k, const float *v, const int64_t *strides,
+                                 int batch, int heads, int sq, int sk, int head_dim, double dropout_p, uint64_t seed,
+                                 float *out, float *lse);
+int mvdetr_attention_forward_f64(void *stream, const double *q, const double *k, const double *v, const int64_t *strides,
+                                 int batch, int heads, int sq, int sk, int head_dim, double dropout_p, uint64_t seed,
+                                 double *out, double *lse);
+int mvdetr_attention_backward_f32(void *stream, const float *grad_out, const float *q, const float *k, const float *v,
+                                  const float *out, const float *lse, const int64_t *strides, int batch, int heads, int sq,
+                                  int sk, int head_dim, double dropout_p, uint64_t seed, void *workspace, float *grad_q,
+                                  float *grad_k, float *grad_v);
+int mvdetr_attention_backward_f64(void *stream, const double *grad_out, const double *q, const double *k, const double *v,
+                                  const double *out, const double *lse, const int64_t *strides, int batch, int heads, int sq,
+                                  int sk, int head_dim, double dropout_p, uint64_t seed, void *workspace, double *grad_q,
+                                  double *grad_k, double *grad_v);
+/* Name of the kernel route the last device attention call of this process took (any thread). Static; never NULL. */
+const char *mvdetr_attention_last_kernel(void);
+
 /* ---- CPU path (host pointers, no stream, synchronous) ------------------------------------------------------------
  * The reference extension raises for CPU tensors (ms_deform_attn_cpu.cpp:17-41 are stubs; ms_deform_attn.h:38,60).
  * These entry points make the same contracts work on host memory: same argument meaning and layouts as the device
@@ -406,6 +445,25 @@ int mvdetr_deform_conv2d_backward_host_f64(const double *grad_out, const double 
                                            int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
                                            int dil_h, int dil_w, int offset_groups, int input_nhwc, double *grad_input,
                                            double *grad_offset, double *grad_weight);
+
+/* attention on host memory: same arguments as the device entries without the stream and the workspace; deterministic; never
+ * more than a 64-key tile of scores per thread.  mvdetr_attention_dropout_mask_host writes the keep decision (1 = kept) of
+ * every element of the [batch, heads, sq, sk] probabilities, as the kernels and the host path make it (tests). */
+int mvdetr_attention_forward_host_f32(const float *q, const float *k, const float *v, const int64_t *strides, int batch,
+                                      int heads, int sq, int sk, int head_dim, double dropout_p, uint64_t seed, float *out,
+                                      float *lse);
+int mvdetr_attention_forward_host_f64(const double *q, const double *k, const double *v, const int64_t *strides, int batch,
+                                      int heads, int sq, int sk, int head_dim, double dropout_p, uint64_t seed, double *out,
+                                      double *lse);
+int mvdetr_attention_backward_host_f32(const float *grad_out, const float *q, const float *k, const float *v, const float *out,
+                                       const float *lse, const int64_t *strides, int batch, int heads, int sq, int sk,
+                                       int head_dim, double dropout_p, uint64_t seed, float *grad_q, float *grad_k,
+                                       float *grad_v);
+int mvdetr_attention_backward_host_f64(const double *grad_out, const double *q, const double *k, const double *v,
+                                       const double *out, const double *lse, const int64_t *strides, int batch, int heads,
+                                       int sq, int sk, int head_dim, double dropout_p, uint64_t seed, double *grad_q,
+                                       double *grad_k, double *grad_v);
+int mvdetr_attention_dropout_mask_host(uint64_t seed, double dropout_p, int batch, int heads, int sq, int sk, uint8_t *mask);
 
 #ifdef __cplusplus
 }

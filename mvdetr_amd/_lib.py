@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # MVDETR_OPS_LIB: another build of the same sources (the phase-stamp build libmvdetr_ops_trace.so of tools/experiments)
 LIB_PATH = os.environ.get("MVDETR_OPS_LIB") or os.path.join(CSRC, "libmvdetr_ops.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _vp, _i = ctypes.c_void_p, ctypes.c_int
 _MSDA_FWD = [_vp] * 6 + [_i] * 7 + [_vp]
@@ -30,6 +30,9 @@ _MSDA_FUSED = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 10 + [_vp]
 _MSDA_FUSED_LEVELS = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 12 + [_vp]
 _DC_FWD = [_vp] * 5 + [_i] * 15 + [_vp]
 _DC_BWD = [_vp] * 5 + [_i] * 15 + [_vp] * 3
+_i64p, _d, _u64 = ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_uint64
+_ATTN_FWD = [_vp] * 4 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 2
+_ATTN_BWD = [_vp] * 7 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 4
 
 SIGNATURES = {
     "mvdetr_ops_abi_version": ([], _i),
@@ -87,6 +90,17 @@ SIGNATURES = {
     "mvdetr_deform_conv2d_forward_host_f64": (_DC_FWD[1:], _i),
     "mvdetr_deform_conv2d_backward_host_f32": (_DC_BWD[1:], _i),
     "mvdetr_deform_conv2d_backward_host_f64": (_DC_BWD[1:], _i),
+    "mvdetr_attention_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_attention_workspace_bytes": ([_i] * 6, ctypes.c_int64),
+    "mvdetr_attention_forward_f32": (_ATTN_FWD, _i),
+    "mvdetr_attention_forward_f64": (_ATTN_FWD, _i),
+    "mvdetr_attention_backward_f32": (_ATTN_BWD, _i),
+    "mvdetr_attention_backward_f64": (_ATTN_BWD, _i),
+    "mvdetr_attention_forward_host_f32": (_ATTN_FWD[1:], _i),
+    "mvdetr_attention_forward_host_f64": (_ATTN_FWD[1:], _i),
+    "mvdetr_attention_backward_host_f32": (_ATTN_BWD[1:15] + _ATTN_BWD[16:], _i),
+    "mvdetr_attention_backward_host_f64": (_ATTN_BWD[1:15] + _ATTN_BWD[16:], _i),
+    "mvdetr_attention_dropout_mask_host": ([_u64, _d] + [_i] * 4 + [_vp], _i),
 }
 
 

@@ -16,13 +16,18 @@
 //   deform_conv  (torchvision.ops.deform_conv2d v1) per batch item and 1024-pixel chunk: the column matrix col[p][c kh kw + tap]
 //             and its gradient g_col are formed with threads owning pixels; grad_weight with threads owning output channels,
 //             grad_input with threads owning input channels.
+//   attention    (softmax(q k^T / sqrt(D)) v, strided operands) forward and dQ: threads own query rows and walk the keys 64 at a
+//             time (online softmax; never more than that tile of scores); dK / dV: threads own key rows and walk the queries,
+//             the probabilities recomputed from lse.  Dropout by the shared counter-based hash (attention_hash.h).
 #include "../../include/mvdetr_ops.h"
+#include "attention_hash.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -536,3 +541,208 @@ MVDETR_DC_HOST_ENTRIES(double, f64)
 
 }  // extern "C"
 
+// ---- attention ------------------------------------------------------------------------------------------------------------
+
+namespace {
+
+struct AtDims {
+    int B, H, Sq, Sk, D;
+    int64_t q[3], k[3], v[3], o[3], go[3], dq[3], dk[3], dv[3];
+    uint32_t thresh;
+    uint64_t seed;
+    double inv_keep;
+};
+
+bool at_dims(const int64_t *strides, int nstr, int B, int H, int Sq, int Sk, int D, double p, uint64_t seed, AtDims &d)
+{
+    if (!strides || B < 0 || H < 0 || Sq < 0 || Sk < 1 || D < 1 || !(p >= 0.0) || !(p < 1.0)) return false;
+    d.B = B; d.H = H; d.Sq = Sq; d.Sk = Sk; d.D = D;
+    int64_t *dst[8] = {d.q, d.k, d.v, d.o, d.go, d.dq, d.dk, d.dv};
+    for (int i = 0; i < 8; ++i)
+        for (int j = 0; j < 3; ++j) dst[i][j] = i < nstr ? strides[3 * i + j] : 0;
+    d.thresh = mvdetr_attn_threshold(p);
+    d.seed = seed;
+    d.inv_keep = 1.0 / (1.0 - p);
+    return true;
+}
+
+inline bool at_keep(const AtDims &d, int b, int h, int i, int j)
+{
+    return mvdetr_attn_hash(d.seed, (((uint64_t)b * d.H + h) * d.Sq + i) * (uint64_t)d.Sk + j) >= d.thresh;
+}
+
+template <typename T> inline T at_dot(const T *a, const T *b, int D)
+{
+    T s = T(0);
+    for (int c = 0; c < D; ++c) s += a[c] * b[c];
+    return s;
+}
+
+constexpr int AT_TILE = 64;         // keys (or queries) whose scores exist at one time
+
+template <typename T> int attention_forward_host(const T *q, const T *k, const T *v, const AtDims &d, T *out, T *lse)
+{
+    const T scale = T(1) / std::sqrt(T(d.D));
+    const bool drop = d.thresh != 0;
+    parallel_ranges((int64_t)d.B * d.H * d.Sq, [=, &d](int64_t first, int64_t last) {
+        std::vector<T> acc(d.D);
+        T s[AT_TILE];
+        for (int64_t row = first; row < last; ++row) {
+            const int i = (int)(row % d.Sq), h = (int)((row / d.Sq) % d.H), b = (int)(row / ((int64_t)d.Sq * d.H));
+            const T *qp = q + b * d.q[0] + h * d.q[1] + i * d.q[2];
+            const T *kb = k + b * d.k[0] + h * d.k[1], *vb = v + b * d.v[0] + h * d.v[1];
+            std::fill(acc.begin(), acc.end(), T(0));
+            T m = -std::numeric_limits<T>::infinity(), l = T(0);
+            for (int j0 = 0; j0 < d.Sk; j0 += AT_TILE) {
+                const int n = std::min(AT_TILE, d.Sk - j0);
+                T mx = m;
+                for (int t = 0; t < n; ++t) {
+                    s[t] = scale * at_dot(qp, kb + (j0 + t) * d.k[2], d.D);
+                    mx = std::max(mx, s[t]);
+                }
+                const T alpha = std::exp(m - mx);              // (0 on the first tile: m = -inf)
+                l *= alpha;
+                for (int c = 0; c < d.D; ++c) acc[c] *= alpha;
+                m = mx;
+                for (int t = 0; t < n; ++t) {
+                    T pv = std::exp(s[t] - m);
+                    l += pv;
+                    if (drop) {
+                        if (!at_keep(d, b, h, i, j0 + t)) continue;
+                        pv *= T(d.inv_keep);
+                    }
+                    const T *vp = vb + (j0 + t) * d.v[2];
+                    for (int c = 0; c < d.D; ++c) acc[c] += pv * vp[c];
+                }
+            }
+            T *op = out + b * d.o[0] + h * d.o[1] + i * d.o[2];
+            for (int c = 0; c < d.D; ++c) op[c] = acc[c] / l;
+            lse[row] = m + std::log(l);
+        }
+    });
+    return 0;
+}
+
+template <typename T>
+int attention_backward_host(const T *go, const T *q, const T *k, const T *v, const T *out, const T *lse, const AtDims &d, T *gq,
+                            T *gk, T *gv)
+{
+    const T scale = T(1) / std::sqrt(T(d.D));
+    const bool drop = d.thresh != 0;
+    const int64_t rows = (int64_t)d.B * d.H * d.Sq;
+    std::vector<T> delta_v(std::max<int64_t>(rows, 1));
+    T *delta = delta_v.data();
+    // dQ (and delta): threads own query rows
+    parallel_ranges(rows, [=, &d](int64_t first, int64_t last) {
+        std::vector<T> acc(d.D);
+        T ds[AT_TILE];
+        for (int64_t row = first; row < last; ++row) {
+            const int i = (int)(row % d.Sq), h = (int)((row / d.Sq) % d.H), b = (int)(row / ((int64_t)d.Sq * d.H));
+            const T *qp = q + b * d.q[0] + h * d.q[1] + i * d.q[2];
+            const T *gp = go + b * d.go[0] + h * d.go[1] + i * d.go[2];
+            const T *kb = k + b * d.k[0] + h * d.k[1], *vb = v + b * d.v[0] + h * d.v[1];
+            const T dl = at_dot(gp, out + b * d.o[0] + h * d.o[1] + i * d.o[2], d.D);
+            delta[row] = dl;
+            std::fill(acc.begin(), acc.end(), T(0));
+            for (int j0 = 0; j0 < d.Sk; j0 += AT_TILE) {
+                const int n = std::min(AT_TILE, d.Sk - j0);
+                for (int t = 0; t < n; ++t) {
+                    const T pv = std::exp(scale * at_dot(qp, kb + (j0 + t) * d.k[2], d.D) - lse[row]);
+                    T dp = at_dot(gp, vb + (j0 + t) * d.v[2], d.D);
+                    if (drop) dp = at_keep(d, b, h, i, j0 + t) ? dp * T(d.inv_keep) : T(0);
+                    ds[t] = pv * (dp - dl);
+                }
+                for (int t = 0; t < n; ++t) {
+                    const T *kp = kb + (j0 + t) * d.k[2];
+                    for (int c = 0; c < d.D; ++c) acc[c] += ds[t] * kp[c];
+                }
+            }
+            T *op = gq + b * d.dq[0] + h * d.dq[1] + i * d.dq[2];
+            for (int c = 0; c < d.D; ++c) op[c] = scale * acc[c];
+        }
+    });
+    // dK, dV: threads own key rows
+    parallel_ranges((int64_t)d.B * d.H * d.Sk, [=, &d](int64_t first, int64_t last) {
+        std::vector<T> ak(d.D), av(d.D);
+        T ds[AT_TILE], pd[AT_TILE];
+        for (int64_t row = first; row < last; ++row) {
+            const int j = (int)(row % d.Sk), h = (int)((row / d.Sk) % d.H), b = (int)(row / ((int64_t)d.Sk * d.H));
+            const T *kp = k + b * d.k[0] + h * d.k[1] + j * d.k[2], *vp = v + b * d.v[0] + h * d.v[1] + j * d.v[2];
+            const T *qb = q + b * d.q[0] + h * d.q[1], *gb = go + b * d.go[0] + h * d.go[1];
+            const int64_t r0 = ((int64_t)b * d.H + h) * d.Sq;
+            std::fill(ak.begin(), ak.end(), T(0));
+            std::fill(av.begin(), av.end(), T(0));
+            for (int i0 = 0; i0 < d.Sq; i0 += AT_TILE) {
+                const int n = std::min(AT_TILE, d.Sq - i0);
+                for (int t = 0; t < n; ++t) {
+                    const int i = i0 + t;
+                    const T pv = std::exp(scale * at_dot(qb + i * d.q[2], kp, d.D) - lse[r0 + i]);
+                    T dp = at_dot(gb + i * d.go[2], vp, d.D);
+                    pd[t] = pv;
+                    if (drop) {
+                        const bool keep = at_keep(d, b, h, i, j);
+                        dp = keep ? dp * T(d.inv_keep) : T(0);
+                        pd[t] = keep ? pv * T(d.inv_keep) : T(0);
+                    }
+                    ds[t] = pv * (dp - delta[r0 + i]);
+                }
+                for (int t = 0; t < n; ++t) {
+                    const T *qp = qb + (i0 + t) * d.q[2], *gp = gb + (i0 + t) * d.go[2];
+                    for (int c = 0; c < d.D; ++c) {
+                        av[c] += pd[t] * gp[c];
+                        ak[c] += ds[t] * qp[c];
+                    }
+                }
+            }
+            T *okp = gk + b * d.dk[0] + h * d.dk[1] + j * d.dk[2], *ovp = gv + b * d.dv[0] + h * d.dv[1] + j * d.dv[2];
+            for (int c = 0; c < d.D; ++c) {
+                okp[c] = scale * ak[c];
+                ovp[c] = av[c];
+            }
+        }
+    });
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdetr_attention_dropout_mask_host(uint64_t seed, double dropout_p, int batch, int heads, int sq, int sk, uint8_t *mask)
+{
+    if (batch < 0 || heads < 0 || sq < 0 || sk < 0 || !(dropout_p >= 0.0) || !(dropout_p < 1.0)) return 1;
+    const int64_t n = (int64_t)batch * heads * sq * sk;
+    if (n == 0) return 0;
+    if (!mask) return 1;
+    const uint32_t thresh = mvdetr_attn_threshold(dropout_p);
+    parallel_ranges(n, [=](int64_t first, int64_t last) {
+        for (int64_t e = first; e < last; ++e) mask[e] = mvdetr_attn_hash(seed, (uint64_t)e) >= thresh ? 1 : 0;
+    });
+    return 0;
+}
+
+#define MVDETR_ATTN_HOST_ENTRIES(T, SFX)                                                                                      \
+    int mvdetr_attention_forward_host_##SFX(const T *q, const T *k, const T *v, const int64_t *strides, int batch, int heads, \
+                                            int sq, int sk, int head_dim, double dropout_p, uint64_t seed, T *out, T *lse)    \
+    {                                                                                                                         \
+        AtDims d;                                                                                                             \
+        if (!at_dims(strides, 4, batch, heads, sq, sk, head_dim, dropout_p, seed, d)) return 1;                               \
+        if ((int64_t)batch * heads * sq == 0) return 0;                                                                       \
+        if (!q || !k || !v || !out || !lse) return 1;                                                                         \
+        return attention_forward_host<T>(q, k, v, d, out, lse);                                                               \
+    }                                                                                                                         \
+    int mvdetr_attention_backward_host_##SFX(const T *grad_out, const T *q, const T *k, const T *v, const T *out,             \
+                                             const T *lse, const int64_t *strides, int batch, int heads, int sq, int sk,      \
+                                             int head_dim, double dropout_p, uint64_t seed, T *grad_q, T *grad_k, T *grad_v)  \
+    {                                                                                                                         \
+        AtDims d;                                                                                                             \
+        if (!at_dims(strides, 8, batch, heads, sq, sk, head_dim, dropout_p, seed, d)) return 1;                               \
+        if (batch * heads == 0) return 0;                                                                                     \
+        if (!k || !v || !grad_k || !grad_v || (sq && (!grad_out || !q || !out || !lse || !grad_q))) return 1;                 \
+        return attention_backward_host<T>(grad_out, q, k, v, out, lse, d, grad_q, grad_k, grad_v);                            \
+    }
+
+MVDETR_ATTN_HOST_ENTRIES(float, f32)
+MVDETR_ATTN_HOST_ENTRIES(double, f64)
+
+}  // extern "C"

@@ -17,7 +17,7 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
-from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat
+from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat, TransformerWorldFeat
 
 
 class BasicBlock(nn.Module):
@@ -178,8 +178,12 @@ class MVDeTr(nn.Module):
         elif world_feat_arch == "deform_conv":
             # the world heads take base_dim channels (mvdetr.py:139-140): the reference's default hidden_dim=128 is base_dim
             self.world_feat = DeformConvWorldFeat(geom.num_cam, geom.Rworld_shape, base_dim, hidden_dim=base_dim)
+        elif world_feat_arch == "trans":
+            # as for deform_conv: the world heads take base_dim channels, and the aggregator views its encoder output with
+            # the input's channel count (trans_world_feat.py:66)
+            self.world_feat = TransformerWorldFeat(geom.num_cam, geom.Rworld_shape, base_dim, hidden_dim=base_dim)
         else:
-            raise ValueError("world_feat_arch must be 'deform_trans', 'conv' or 'deform_conv'")
+            raise ValueError("world_feat_arch must be 'deform_trans', 'conv', 'deform_conv' or 'trans'")
         self.world_heatmap = output_head(base_dim, outfeat_dim, 1)
         self.world_offset = output_head(base_dim, outfeat_dim, 2)
         # init (mvdetr.py:142-148)

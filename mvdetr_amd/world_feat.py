@@ -4,6 +4,8 @@ Mirrors, with identical parameter names (reference checkpoints load unchanged):
   * create_pos_embedding                 multiview_detector/models/trans_world_feat.py:15-37
   * DeformTransWorldFeat                 multiview_detector/models/trans_world_feat.py:70-119
   * DeformableTransformerEncoder(Layer)  multiview_detector/models/deformable_transformer.py:22-85
+  * TransformerWorldFeat                 multiview_detector/models/trans_world_feat.py:40-67
+  * TransformerEncoder(Layer)            multiview_detector/models/transformer.py:18-65
 
 Deliberate differences:
   * B > 1 works (the reference reshapes the level embedding with the batch size and fails,
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .ops.add_layernorm import add_layer_norm, fused_add_layer_norm_available
+from .ops.attention import MultiheadAttention
 from .ops.deform_conv import DeformConv2d
 from .ops.modules import MSDeformAttn
 
@@ -274,3 +277,84 @@ class DeformConvWorldFeat(nn.Module):
             pos = self.deform_pos[n](feat)
             feats.append(F.relu(self.deform_conv[n](feat, pos)))
         return self.world_feat(self.merge_linear(torch.cat(feats, dim=1)))
+
+
+class TransformerEncoderLayer(nn.Module):
+    """The DETR encoder layer of the reference's ``trans`` aggregator (models/transformer.py:37-65): post-norm,
+    ``q = k = src + pos``, ``value = src``; tokens seq-first [S, B, C].  ``self_attn`` is ops.MultiheadAttention (state-dict
+    compatible with nn.MultiheadAttention), called without weights: the fused kernels of csrc/attention.hip."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1):
+        super().__init__()
+        self.self_attn = MultiheadAttention(d_model, nhead, dropout=dropout)
+        self.linear1 = nn.Linear(d_model, dim_feedforward)
+        self.dropout = nn.Dropout(dropout)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        self.norm1 = nn.LayerNorm(d_model)
+        self.norm2 = nn.LayerNorm(d_model)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+
+    @staticmethod
+    def with_pos_embed(tensor, pos):
+        return tensor if pos is None else tensor + pos
+
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, pos=None):
+        q = k = self.with_pos_embed(src, pos)
+        # masks (never passed by the aggregator) need torch's path, which returns the weights as the reference's call does
+        fused = src_mask is None and src_key_padding_mask is None
+        src2 = self.self_attn(q, k, value=src, attn_mask=src_mask, key_padding_mask=src_key_padding_mask,
+                              need_weights=not fused)[0]
+        src = self.norm1(src + self.dropout1(src2))
+        src2 = self.linear2(self.dropout(F.relu(self.linear1(src))))
+        return self.norm2(src + self.dropout2(src2))
+
+
+class TransformerEncoder(nn.Module):
+    """models/transformer.py:18-34: the layers in sequence, no final norm."""
+
+    def __init__(self, encoder_layer, num_layers):
+        super().__init__()
+        self.layers = nn.ModuleList([copy.deepcopy(encoder_layer) for _ in range(num_layers)])
+        self.num_layers = num_layers
+
+    def forward(self, src, mask=None, src_key_padding_mask=None, pos=None):
+        output = src
+        for layer in self.layers:
+            output = layer(output, src_mask=mask, src_key_padding_mask=src_key_padding_mask, pos=pos)
+        return output
+
+
+class TransformerWorldFeat(nn.Module):
+    """The reference's ``--world_feat trans`` aggregator (multiview_detector/models/trans_world_feat.py:40-67, same submodule
+    names): the cameras' features are concatenated along the channel axis and reduced to 1/4 resolution by two stride-2 3x3
+    convolutions; three plain transformer encoder layers attend over ALL cells of that grid (2,700 tokens at Wildtrack size)
+    with a sine position embedding added to queries and keys; two bilinear upsample + 3x3 conv stages return to the world
+    grid.  The position embedding is a non-persistent buffer (a plain attribute in the reference), so a reference checkpoint
+    loads with strict=True.  Like the reference (l.66 views the encoder output with the input's channel count) it needs
+    hidden_dim == base_dim.  B > 1 works."""
+
+    def __init__(self, num_cam, Rworld_shape, base_dim, hidden_dim=128, dropout=0.1, nhead=8, dim_feedforward=512):
+        super().__init__()
+        if hidden_dim != base_dim:
+            raise ValueError("TransformerWorldFeat needs hidden_dim == base_dim (trans_world_feat.py:66)")
+        self.num_cam, self.base_dim, self.hidden_dim = num_cam, base_dim, hidden_dim
+        H, W = int(Rworld_shape[0]), int(Rworld_shape[1])
+        self.downsample = nn.Sequential(nn.Conv2d(base_dim * num_cam, hidden_dim, 3, 2, 1), nn.ReLU(),
+                                        nn.Conv2d(hidden_dim, hidden_dim, 3, 2, 1), nn.ReLU())
+        self.register_buffer("pos_embedding", create_pos_embedding((-(-H // 4), -(-W // 4)), hidden_dim // 2),
+                             persistent=False)
+        layer = TransformerEncoderLayer(d_model=hidden_dim, dropout=dropout, nhead=nhead, dim_feedforward=dim_feedforward)
+        self.encoder = TransformerEncoder(layer, 3)
+        self.upsample = nn.Sequential(nn.Upsample([-(-H // 2), -(-W // 2)], mode="bilinear"),
+                                      nn.Conv2d(hidden_dim, hidden_dim, 3, 1, 1), nn.ReLU(),
+                                      nn.Upsample([H, W], mode="bilinear"),
+                                      nn.Conv2d(hidden_dim, hidden_dim, 3, 1, 1), nn.ReLU())
+
+    def forward(self, x, visualize=False):
+        B, N, C, H, W = x.shape
+        x = self.downsample(x.reshape(B, N * C, H, W))
+        h, w = x.shape[-2:]
+        pos = self.pos_embedding.flatten(2).permute(2, 0, 1)                 # [h*w, 1, C], broadcast over the batch
+        x = self.encoder(x.flatten(2).permute(2, 0, 1), pos=pos)            # tokens seq-first [h*w, B, C]
+        return self.upsample(x.permute(1, 2, 0).reshape(B, C, h, w))
