@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_* */
+#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -266,6 +266,31 @@ int mvdetr_add_layernorm_f32(void *stream, const float *x, const float *residual
 int mvdetr_add_layernorm_add_f32(void *stream, const float *x, const float *residual, const float *weight,
                                  const float *bias, const float *add2, int64_t add2_rows, int64_t rows, int cols,
                                  float eps, float *out, float *out2);
+
+/* ---- The ResNet trunk's inference epilogues (csrc/trunk_epilogue.hip) ---------------------------
+ * Eval-mode BatchNorm2d with what follows it in a residual block, one pass over channel-last fp32 activations:
+ *     y[r, c] = act( x[r, c]*s[c] + t[c]  [+ res[r, c]]  [+ res[r, c]*s2[c] + t2[c]] )
+ *     s = gamma / sqrt(var + eps),  t = beta - mean*s     (formed in the kernel on every call; gamma / beta NULL: 1 / 0)
+ *   x, res, y   [rows, channels] fp32, 16-byte aligned (NHWC memory: rows = N*H*W); y may be x (in place), res may not be y
+ *   res         NULL: no residual.  With every res_* NULL it is added as is (the identity branch); with res_mean / res_var
+ *               (and optionally res_gamma / res_beta) it goes through its own BatchNorm first (the downsample branch)
+ *   relu        non-zero: act = ReLU with torch's NaN rule (relu(NaN) = NaN); zero: none
+ * channels must be a multiple of 4.  hipErrorInvalidValue (1) for anything else that does not fit. */
+int mvdetr_bn_act_f32(void *stream, const float *x, const float *mean, const float *var, const float *gamma,
+                      const float *beta, float eps, const float *res, const float *res_mean, const float *res_var,
+                      const float *res_gamma, const float *res_beta, float res_eps, int64_t rows, int channels, int relu,
+                      float *y);
+/* The stem: MaxPool2d(kernel 3, stride 2, padding 1) over relu(BatchNorm(x)) in one pass.
+ *   x [n, h, w, channels], y [n, (h-1)/2+1, (w-1)/2+1, channels] fp32 NHWC, 16-byte aligned, not overlapping
+ * Padding counts as -inf and a NaN in the window gives NaN, as in torch.  channels/4 must divide 256 or be a multiple of
+ * it (64, 128, ..., 1024, 2048, ...): hipErrorNotSupported (801) otherwise. */
+int mvdetr_bn_relu_maxpool_f32(void *stream, const float *x, const float *mean, const float *var, const float *gamma,
+                               const float *beta, float eps, int n, int h, int w, int channels, float *y);
+/* Name of the kernel the last trunk-epilogue call of this process launched ("bn_relu", "bn_add_relu", "bn_bn_add_relu",
+ * "bn_relu_maxpool", ...; "none" before the first), and how many such launches there have been: tests tell the fused
+ * path from torch's ops by them.  Static storage; never NULL. */
+const char *mvdetr_trunk_last_kernel(void);
+int64_t mvdetr_trunk_launch_count(void);
 
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------
  * Name of the kernel variant the last forward call ON THIS THREAD dispatched to

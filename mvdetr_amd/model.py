@@ -1,6 +1,7 @@
 """Minimal caller of the fusion path: an MVDeTr-shaped detector whose warp and deformable attention
-run on the HIP kernels.  Everything that is not the hot path (ResNet-18 trunk, heads) is ordinary
-PyTorch-ROCm, as in the reference.
+run on the HIP kernels.  The trunk's and the heads' convolutions are ordinary PyTorch-ROCm, as in the
+reference; in inference the trunk's BatchNorm / ReLU / residual-add / max-pool passes between them run
+fused on HIP kernels (ops/trunk_epilogue.py), and as the modules' own torch ops everywhere else.
 
 Mirrors multiview_detector/models/mvdetr.py:74-218 (constructor arithmetic, forward order, output
 tuple) and the dilated ResNet-18 trunk of multiview_detector/models/resnet.py:33-70,120-186
@@ -17,7 +18,53 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
+from .ops.trunk_epilogue import bn_act, bn_relu_maxpool, fused_bn_act_available, fused_bn_relu_maxpool_available
 from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat, TransformerWorldFeat
+
+
+def _bn_relu(out, bn, relu):
+    """relu(bn(out)) for a convolution's fresh output: one in-place HIP pass in inference, torch's ops otherwise."""
+    if type(relu) is nn.ReLU and fused_bn_act_available(out, bn):
+        return bn_act(out, bn, relu=True, inplace=True)
+    return relu(bn(out))
+
+
+def _bn_add_relu(out, bn, x, downsample, relu):
+    """The tail of a residual block, relu(bn(out) + identity), where identity is the block's input x or
+    downsample(x) = BatchNorm(1x1 convolution(x)).  In inference one HIP pass over ``out`` (the last convolution's
+    fresh output, overwritten in place) that reads the identity branch -- the downsample convolution's raw output goes
+    through its BatchNorm in the same pass; x itself is never written.  torch's ops otherwise, as in the reference."""
+    if type(relu) is nn.ReLU:
+        if downsample is None:
+            if fused_bn_act_available(out, bn, x):
+                return bn_act(out, bn, x, relu=True, inplace=True)
+        elif type(downsample) is nn.Sequential and len(downsample) == 2 and type(downsample[0]) is nn.Conv2d \
+                and fused_bn_act_available(out, bn):
+            raw = downsample[0](x)
+            if fused_bn_act_available(out, bn, raw, downsample[1]):
+                return bn_act(out, bn, raw, downsample[1], relu=True, inplace=True)
+            return relu(bn(out) + downsample[1](raw))
+    identity = x if downsample is None else downsample(x)
+    return relu(bn(out) + identity)
+
+
+class ResNetTrunk(nn.Sequential):
+    """The trunk as the reference slices it -- conv1, bn1, relu, maxpool, layer1..4 at child indices 0..7, so parameter
+    names are ``base.<index>...`` -- whose forward runs children 1-3 (BatchNorm, ReLU, MaxPool2d(3, 2, 1)) as one HIP
+    pass over the stem convolution's output when that is eligible, and child by child otherwise."""
+
+    def forward(self, x):
+        mods = list(self)
+        if len(mods) >= 4 and type(mods[0]) is nn.Conv2d:
+            x = mods[0](x)
+            if fused_bn_relu_maxpool_available(x, mods[1], mods[2], mods[3]):
+                x = bn_relu_maxpool(x, mods[1])
+                mods = mods[4:]
+            else:
+                mods = mods[1:]
+        for m in mods:
+            x = m(x)
+        return x
 
 
 class BasicBlock(nn.Module):
@@ -33,10 +80,8 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
-        return self.relu(out + identity)
+        out = _bn_relu(self.conv1(x), self.bn1, self.relu)
+        return _bn_add_relu(self.conv2(out), self.bn2, x, self.downsample, self.relu)
 
 
 class Bottleneck(nn.Module):
@@ -57,11 +102,9 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
-        return self.relu(out + identity)
+        out = _bn_relu(self.conv1(x), self.bn1, self.relu)
+        out = _bn_relu(self.conv2(out), self.bn2, self.relu)
+        return _bn_add_relu(self.conv3(out), self.bn3, x, self.downsample, self.relu)
 
 
 def resnet_trunk(depth=18, replace_stride_with_dilation=(False, True, True), in_channels=3) -> nn.Sequential:
@@ -85,7 +128,7 @@ def resnet_trunk(depth=18, replace_stride_with_dilation=(False, True, True), in_
         layers += [block(planes * exp, planes, dilation=state["dilation"]) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
-    trunk = nn.Sequential(
+    trunk = ResNetTrunk(
         nn.Conv2d(in_channels, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True),
         nn.MaxPool2d(3, 2, 1),
         make_layer(64, counts[0]), make_layer(128, counts[1], 2, replace_stride_with_dilation[0]),
