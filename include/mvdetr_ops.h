@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load) */
+#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -420,6 +420,60 @@ int mvdetr_attention_backward_f64(void *stream, const double *grad_out, const do
                                   double *grad_k, double *grad_v);
 /* Name of the kernel route the last device attention call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_attention_last_kernel(void);
+
+/* ---- Detection objective: focal loss over heat maps, masked L1 at gathered positions ------------------------------
+ * (csrc/detection_loss.hip; additive entries, the ABI version above is unchanged.)  The formulas are those of the
+ * reference's loss/losses.py:17-64.  One call is ONE kernel launch over `nseg` <= MVDETR_LOSS_MAX_SEGMENTS segments;
+ * `segs` is a HOST array that is copied into the kernel arguments (nothing is uploaded), every other pointer, and every
+ * pointer inside a segment, is a device pointer.  `_f32` / `_f64` is the element type of logits / output, target, mask (focal)
+ * and the gradients.  Results stay on the device: out[0 .. nseg-1] the segments' losses, out[nseg] = sum_s weight_s * loss_s.
+ * `stats` [nseg] fp64 is written by the forward (focal: num_pos; L1: the denominator) and read by the backward, whose
+ * grad_out is the [nseg + 1] gradient of `out`.  No host synchronisation, no floating-point atomics: bit-reproducible.
+ *   stride / grad_stride: element strides of the [batch, channels, height, width] tensor and of its gradient (any layout).
+ *   focal: target and mask (NULL: none; it multiplies the negative term) are dense NCHW of the same shape.
+ *   L1: mask [batch, k] bytes, ind [batch, k] int64 = y * width + x (entries outside the map are never dereferenced and
+ *       contribute nothing), target [batch, k, channels] dense; k <= 1024.
+ *   grad: written entirely by the backward (NULL: that segment gets no gradient); ignored by the forward.
+ *   workspace: mvdetr_focal_loss_workspace_bytes(...) bytes, 8-byte aligned, contents arbitrary.
+ *   counters: MVDETR_LOSS_MAX_SEGMENTS + 1 int32, ZERO on entry; the kernel leaves them zero, so one buffer per stream
+ *       can be reused call after call.
+ * Kernel names: "focal_loss_fwd", "focal_loss_bwd", "reg_l1_loss_fwd", "reg_l1_loss_bwd". */
+#define MVDETR_LOSS_MAX_SEGMENTS 4
+typedef struct {
+    const void *logits, *target, *mask;
+    void *grad;
+    int64_t stride[4], grad_stride[4];
+    int batch, channels, height, width;
+    double weight;
+} mvdetr_focal_segment;
+typedef struct {
+    const void *output;
+    const uint8_t *mask;
+    const int64_t *ind;
+    const void *target;
+    void *grad;
+    int64_t stride[4], grad_stride[4];
+    int batch, channels, height, width, k;
+    double weight;
+} mvdetr_l1_segment;
+int64_t mvdetr_focal_loss_workspace_bytes(const mvdetr_focal_segment *segs, int nseg, int elem_size);
+int mvdetr_focal_loss_forward_f32(void *stream, const mvdetr_focal_segment *segs, int nseg, void *workspace, int32_t *counters,
+                                  float *out, double *stats);
+int mvdetr_focal_loss_forward_f64(void *stream, const mvdetr_focal_segment *segs, int nseg, void *workspace, int32_t *counters,
+                                  double *out, double *stats);
+int mvdetr_focal_loss_backward_f32(void *stream, const mvdetr_focal_segment *segs, int nseg, const float *grad_out,
+                                   const double *stats);
+int mvdetr_focal_loss_backward_f64(void *stream, const mvdetr_focal_segment *segs, int nseg, const double *grad_out,
+                                   const double *stats);
+int mvdetr_reg_l1_loss_forward_f32(void *stream, const mvdetr_l1_segment *segs, int nseg, float *out, double *stats);
+int mvdetr_reg_l1_loss_forward_f64(void *stream, const mvdetr_l1_segment *segs, int nseg, double *out, double *stats);
+int mvdetr_reg_l1_loss_backward_f32(void *stream, const mvdetr_l1_segment *segs, int nseg, const float *grad_out,
+                                    const double *stats);
+int mvdetr_reg_l1_loss_backward_f64(void *stream, const mvdetr_l1_segment *segs, int nseg, const double *grad_out,
+                                    const double *stats);
+/* Name of the kernel the last loss call of this process launched ("none" before the first), and the number of launches. */
+const char *mvdetr_loss_last_kernel(void);
+int64_t mvdetr_loss_launch_count(void);
 
 /* ---- CPU path (host pointers, no stream, synchronous) ------------------------------------------------------------
  * The reference extension raises for CPU tensors (ms_deform_attn_cpu.cpp:17-41 are stubs; ms_deform_attn.h:38,60).

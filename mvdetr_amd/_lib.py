@@ -34,6 +34,24 @@ _i64p, _d, _u64 = ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_uint
 _ATTN_FWD = [_vp] * 4 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 2
 _ATTN_BWD = [_vp] * 7 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 4
 
+
+class FocalSegment(ctypes.Structure):
+    """mvdetr_focal_segment of the header: one heat map of a focal-loss launch."""
+    _fields_ = [("logits", _vp), ("target", _vp), ("mask", _vp), ("grad", _vp), ("stride", ctypes.c_int64 * 4),
+                ("grad_stride", ctypes.c_int64 * 4), ("batch", _i), ("channels", _i), ("height", _i), ("width", _i),
+                ("weight", _d)]
+
+
+class L1Segment(ctypes.Structure):
+    """mvdetr_l1_segment of the header: one regression map of a masked-L1 launch."""
+    _fields_ = [("output", _vp), ("mask", _vp), ("ind", _vp), ("target", _vp), ("grad", _vp), ("stride", ctypes.c_int64 * 4),
+                ("grad_stride", ctypes.c_int64 * 4), ("batch", _i), ("channels", _i), ("height", _i), ("width", _i), ("k", _i),
+                ("weight", _d)]
+
+
+LOSS_MAX_SEGMENTS = 4
+_FSEG, _LSEG = ctypes.POINTER(FocalSegment), ctypes.POINTER(L1Segment)
+
 SIGNATURES = {
     "mvdetr_ops_abi_version": ([], _i),
     "mvdetr_msda_last_forward_impl": ([], ctypes.c_char_p),
@@ -105,6 +123,17 @@ SIGNATURES = {
     "mvdetr_attention_backward_host_f32": (_ATTN_BWD[1:15] + _ATTN_BWD[16:], _i),
     "mvdetr_attention_backward_host_f64": (_ATTN_BWD[1:15] + _ATTN_BWD[16:], _i),
     "mvdetr_attention_dropout_mask_host": ([_u64, _d] + [_i] * 4 + [_vp], _i),
+    "mvdetr_focal_loss_workspace_bytes": ([_FSEG, _i, _i], ctypes.c_int64),
+    "mvdetr_focal_loss_forward_f32": ([_vp, _FSEG, _i, _vp, _vp, _vp, _vp], _i),
+    "mvdetr_focal_loss_forward_f64": ([_vp, _FSEG, _i, _vp, _vp, _vp, _vp], _i),
+    "mvdetr_focal_loss_backward_f32": ([_vp, _FSEG, _i, _vp, _vp], _i),
+    "mvdetr_focal_loss_backward_f64": ([_vp, _FSEG, _i, _vp, _vp], _i),
+    "mvdetr_reg_l1_loss_forward_f32": ([_vp, _LSEG, _i, _vp, _vp], _i),
+    "mvdetr_reg_l1_loss_forward_f64": ([_vp, _LSEG, _i, _vp, _vp], _i),
+    "mvdetr_reg_l1_loss_backward_f32": ([_vp, _LSEG, _i, _vp, _vp], _i),
+    "mvdetr_reg_l1_loss_backward_f64": ([_vp, _LSEG, _i, _vp, _vp], _i),
+    "mvdetr_loss_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_loss_launch_count": ([], ctypes.c_int64),
 }
 
 
