@@ -4,7 +4,17 @@ DeformConvWorldFeat aggregator and MVDeTr(world_feat_arch="deform_conv") on CPU 
 fp32 bars follow the error of the fp32 arithmetic: a sum of K = C_in * kh * kw products accumulated in order errs by
 about K * 2^-24 * sum|w * sample|; each bilinear sample adds a few roundings of its own (+8 below); the fp32 sampling
 position y = (h * s - p + i * d) + dy is rounded once, 2^-24 * |y| px, which moves a sample by at most that times
-|v_hi - v_lo| <= 2 max|x| per axis."""
+|v_hi - v_lo| <= 2 max|x| per axis.
+
+The geometry matrix (tests/deform_conv_cases.py: kernels 1x1 .. 5x5 and 5x3, strides with and without a remainder,
+anisotropic stride / padding / dilation, padding 0 and beyond the kernel's reach, one and two offset groups) runs the host
+path in fp64 (<= 1e-10 (1 + max|want|)) and in fp32 against that module's per-element bars, for the output and all four
+gradients, with +-3 px random offsets, with dyadic offsets (multiples of 1/4: no mask, taps exactly on integers, on -1 and
+on H) and with NaN / inf / 1e9 offsets.  Largest host fp32 err / bar over the matrix (NCHW and channel-last, random and
+dyadic): out 0.44, grad_input 0.60, grad_offset 0.56, grad_weight 0.12, grad_bias 0.27.  Every mutant of that module
+exceeds every bar it touches (test_mutants_exceed_every_bar_they_touch, over elements whose bar is not 0); the smallest
+margins are out 5.7x (positions shifted, k3_d2_c160), grad_input 10x and grad_offset 13x (one grad_out element dropped,
+k3_default), grad_weight 9.7x (positions shifted, k3_c128_18x40) and grad_bias 140x."""
 import inspect
 import math
 
@@ -12,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import deform_conv_cases as cases
 from deform_conv_oracle import deform_conv2d as oracle
 from deform_conv_oracle import with_grads
 
@@ -247,3 +258,99 @@ def test_mini_deform_conv_model_runs_forward_and_backward_on_the_cpu():
                  "world_feat.merge_linear.0.weight", "base.0.weight"):
         grad = dict(model.named_parameters())[name].grad
         assert grad is not None and torch.isfinite(grad).all() and grad.abs().sum().item() > 0, name
+
+
+# ---- the geometry matrix on the host path ---------------------------------------------------------------------------------
+
+CASE_IDS = [c.name for c in cases.MATRIX]
+
+
+def _typed(tensors, dtype, cl):
+    x, *rest = (t.to(dtype) for t in tensors)
+    return [x.contiguous(memory_format=torch.channels_last) if cl else x] + rest
+
+
+@pytest.mark.parametrize("cl", [False, True], ids=["nchw", "cl"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", CASE_IDS)
+def test_matrix_host_path_matches_the_oracle(name, dtype, cl):
+    """Output and all four gradients over the geometry matrix with +-3 px random offsets.  The offsets must exercise full,
+    partial and empty footprints, and the mask of the offset-gradient comparison (taps within 1e-4 px of an integer or of
+    the -1 / H edges, where fp32 rounding can flip the floor) must keep at least 99 % of the taps."""
+    case = cases.by_name(name)
+    inputs, want, bar = cases.matrix_reference(name, "random")
+    full, partial, outside = cases.tap_classes(case, inputs[1])
+    assert full.any() and partial.any() and outside.any(), (int(full.sum()), int(partial.sum()), int(outside.sum()))
+    keep = cases.smooth_mask(case, inputs[1])
+    assert keep.float().mean().item() >= 0.99
+    got = cases.run(_lib_op(), *_typed(inputs, dtype, cl), case)
+    cases.check_against_oracle(f"host {name}", got, want, bar, dtype, cases.tap_mask_to_channels(keep))
+
+
+@pytest.mark.parametrize("cl", [False, True], ids=["nchw", "cl"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", [c.name for c in cases.DYADIC_CASES])
+def test_dyadic_offsets_match_the_oracle_without_a_mask(name, dtype, cl):
+    """Offsets that are multiples of 1/4: every position is exact in fp32, so nothing is masked -- the one-sided derivative
+    at integer coordinates and the zero sample exactly on y = -1 and y = H are compared as they are."""
+    case = cases.by_name(name)
+    inputs, want, bar = cases.matrix_reference(name, "dyadic")
+    on_integer, on_minus_one, on_far_edge = cases.on_grid(case, inputs[1])
+    assert on_integer > 0 and on_minus_one > 0 and on_far_edge > 0, (on_integer, on_minus_one, on_far_edge)
+    got = cases.run(_lib_op(), *_typed(inputs, dtype, cl), case)
+    cases.check_against_oracle(f"host dyadic {name}", got, want, bar, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", cases.NONFINITE_IDS)
+def test_nonfinite_and_huge_offsets_sample_zero(name, dtype):
+    """A tap whose offset is NaN, +-inf or +-1e9 samples 0: the result is the oracle's with that tap far outside, finite
+    everywhere, with a zero offset gradient at the tap."""
+    case = cases.by_name(name)
+    inputs = cases.nonfinite_reference(name)[0]
+    assert not torch.isfinite(inputs[1]).all() and (inputs[1].abs() == 1e9).any()
+    got = cases.run(_lib_op(), *_typed(inputs, dtype, False), case)
+    cases.check_nonfinite(f"host nonfinite {name}", got, name, dtype)
+
+
+@pytest.mark.parametrize("name", CASE_IDS + [c.name for c in cases.BAR_ONLY_CASES])
+def test_mutants_exceed_every_bar_they_touch(name):
+    """The bars must catch a subtly wrong implementation: each mutant (cases.MUTANTS, made from the oracle alone) errs by
+    more than the bar in at least one element of every tensor it touches."""
+    case = cases.by_name(name)
+    inputs, want, bar = cases.matrix_reference(name, "random")
+    applied = 0
+    for mutant, fn in cases.MUTANTS.items():
+        wrong = fn(case, *inputs)
+        if wrong is None:                                  # equal to the truth by construction on this geometry
+            continue
+        applied += 1
+        r = cases.ratios([t if m is None else m for m, t in zip(wrong, want)], want, bar, positive_bar_only=True)
+        for tensor in cases.MUTANT_TOUCHES[mutant]:
+            assert r[tensor] > 1.0, f"mutant {mutant} passes the {tensor} bar on {name}: err / bar = {r[tensor]:.3f}"
+    assert applied >= 6
+
+
+def test_every_mutant_applies_somewhere():
+    for mutant, fn in cases.MUTANTS.items():
+        assert any(fn(c, *cases.matrix_reference(c.name, "random")[0]) is not None for c in cases.MATRIX if c.C <= 6), mutant
+
+
+def test_matrix_holds_the_geometries_and_launch_structures_it_is_for():
+    """The matrix is shared with the GPU tests: what they rely on being in it is pinned here."""
+    m = cases.MFMA_CASES
+    assert {(c.kh, c.kw) for c in m} >= {(1, 1), (1, 3), (3, 1), (2, 2), (5, 5), (5, 3), (3, 3)}
+    assert all(c.offset_groups == 1 and c.C % 16 == 0 and c.C_out % 32 == 0 for c in m)                  # the MFMA route
+    assert all(c.C % 2 == 1 or c.offset_groups == 2 for c in cases.GENERIC_CASES)
+    assert [c._replace(name="", C=0, C_out=0, offset_groups=0) for c in m] == \
+        [c._replace(name="", C=0, C_out=0, offset_groups=0) for c in cases.GENERIC_CASES]                  # twins: same geometry
+    rem = lambda c, a: (c[8 + a] + 2 * c.padding[a] - c.dilation[a] * (c[1 + a] - 1) - 1) % c.stride[a]  # noqa: E731
+    assert any(c.stride == (2, 2) and rem(c, 0) for c in m) and any(c.stride == (2, 2) and not rem(c, 0) and not rem(c, 1) for c in m)
+    assert any(len({c.stride[0], c.stride[1]}) == 2 and c.padding[0] != c.padding[1] and c.dilation[0] != c.dilation[1] for c in m)
+    assert any(c.dilation == (2, 2) for c in m) and any(c.padding == (0, 0) for c in m)
+    assert any(c.padding[0] > c.dilation[0] * (c.kh - 1) for c in m)
+    assert all(c.B >= 2 and (c.out_hw[0] * c.out_hw[1]) % 32 for c in m if c.name != "k3_s2_tiny")
+    assert {c.C_out for c in m} >= {160, 256} and any(c.C == 160 and c.C_out == 160 for c in m)
+    assert any(c.B * c.out_hw[0] * c.out_hw[1] <= 32 for c in m)                                         # one 32-pixel chunk
+    assert any(c.C == 16 and c.stride != (1, 1) for c in m)                                              # dc_fwd_mfma<16>
+    assert any(c.out_hw != (c.H, c.W) for c in m)

@@ -1,16 +1,24 @@
 """Deformable convolution on the MI355X: the MFMA implicit-GEMM route and the generic kernels against the fp64 restatement
 (tests/deform_conv_oracle.py), the route pinned by last_kernel, and the deform_conv model on the GPU vs the CPU.
 
-Bars: forward per element from the fp32 error model of tests/test_deform_conv.py (fp32_bar).  Gradients per tensor:
-2^-24 * (chain length + position term) * the largest bound of the same quantity with |.| operands, where taps within 1e-4 px
-of an integer coordinate or of the -1 / H edge are masked out of the offset-gradient comparison (the derivative is one-sided
-there)."""
+Bars: per element, from the fp32 error model of tests/deform_conv_cases.py (forward, grad_input, grad_offset, grad_weight,
+grad_bias; the large forward-only cases keep fp32_bar of tests/test_deform_conv.py, whose operands fit in memory there).
+Taps within 1e-4 px of an integer coordinate or of the -1 / H edge are masked out of the offset-gradient comparison when
+the offsets are random (fp32 rounding can flip the floor there); the dyadic cases compare every tap.
+
+The geometry matrix of tests/deform_conv_cases.py runs forward and backward on dc_*_mfma (channel-last, and NCHW for a few)
+and on dc_*_generic (the fp32 twins, and fp64 on every shape); among its MFMA cases are the launch structures C_out = 160
+and 256 (blockIdx.y > 0), C = C_out = 160, an output of 24 pixels (dc_bwd_weight_mfma's single-range direct store),
+C = 16 under stride 2 (dc_fwd_mfma<16>) and pixel tiles that straddle batch items.  Every check prints its largest
+err / bar per tensor before it asserts (pytest -s)."""
 import pytest
 import torch
 import torch.nn.functional as F
 
-from deform_conv_oracle import positions, with_grads
+import deform_conv_cases as cases
+from deform_conv_oracle import with_grads
 from deform_conv_oracle import deform_conv2d as oracle
+from deform_conv_cases import NONFINITE_IDS, check_against_oracle, check_nonfinite, matrix_reference, nonfinite_reference
 from test_deform_conv import EPS32, fp32_bar
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +58,11 @@ def _forward_check(x, off, w, b, cl=True, want_kernel="dc_fwd_mfma", padding=1, 
     err = (got.cpu().double() - want).abs()
     bar = fp32_bar(x, off, w, stride, padding, dilation)
     assert (err <= bar).all(), (err.max().item(), (err / bar).max().item())
+    case = _case_of(x, off, w, stride, padding, dilation)
+    if x.shape[1] * off.shape[1] * off.shape[0] * off.shape[2] * off.shape[3] <= 1 << 22:   # the per-element bar's operands fit
+        bar = cases.bars(case, x, off, w, b, torch.zeros(got.shape))["out"]
+        print(f"DCBAR {want_kernel} forward {tuple(x.shape)} out={(err / bar).max().item():.4f}")
+        assert (err <= bar).all(), (err.max().item(), (err / bar).max().item())
     return got
 
 
@@ -101,51 +114,90 @@ def test_zero_offsets_match_conv2d_on_the_device():
     assert ((got.double() - want).abs() <= bar).all()
 
 
-def _smooth_mask(off, k, H, W, tol=1e-4):
-    """[B, T, Ho, Wo] True where the tap's y and x are more than tol px from an integer and from the -1 / H edges."""
-    y, x = positions(off, k, k, 1, 1, 1)
-
-    def ok(v, n):
-        frac = v - torch.floor(v)
-        return (frac > tol) & (frac < 1 - tol) & ((v + 1).abs() > tol) & ((v - n).abs() > tol)
-    return ok(y, H) & ok(x, W)
+def _case_of(x, off, w, stride, padding, dilation):
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)                                          # noqa: E731
+    Co, C, kh, kw = w.shape
+    return cases.Case("adhoc", kh, kw, pair(stride), pair(padding), pair(dilation), C, Co, x.shape[2], x.shape[3], x.shape[0],
+                      off.shape[1] // (2 * kh * kw))
 
 
-def _grad_check(x, off, w, b, cl, want_kernel):
-    dc = _ops()
-    k = w.shape[-1]
-    Co, C = w.shape[:2]
-    H, W = x.shape[-2:]
+def _grad_check(x, off, w, b, cl, want_kernel, stride=1, padding=1, dilation=1):
+    """All four gradients for a random grad_out of the output's shape, every element inside its bar."""
+    case = _case_of(x, off, w, stride, padding, dilation)
+    assert tuple(off.shape[2:]) == case.out_hw
     g = torch.Generator().manual_seed(11)
-    gout = torch.randn(x.shape[0], Co, H, W, generator=g)
-    xd = x.to(DEV)
+    gout = torch.randn(x.shape[0], w.shape[0], *case.out_hw, generator=g)
+    got = _run(case, (x, off, w, b, gout), torch.float32, cl, want_kernel[len("dc_bwd_"):])
+    want = with_grads(x, off, w, b, gout, **case.conf)
+    mask = cases.smooth_mask(case, off)
+    assert mask.float().mean().item() >= 0.99
+    check_against_oracle(f"{want_kernel} {tuple(x.shape)}", got, want, cases.bars(case, x, off, w, b, gout), torch.float32,
+                         cases.tap_mask_to_channels(mask))
+
+
+def _run(case, inputs, dtype, cl, route):
+    """Forward and backward on the device with both routes pinned; (out, grad_input, grad_offset, grad_weight, grad_bias)."""
+    dc = _ops()
+    x, off, w, b, gout = (t.to(dtype).to(DEV) for t in inputs)
     if cl:
-        xd = xd.contiguous(memory_format=torch.channels_last)
-    leaves = [t.detach().requires_grad_(True) for t in (xd, off.to(DEV), w.to(DEV), b.to(DEV))]
-    dc.deform_conv2d(*leaves, padding=1).backward(gout.to(DEV))
+        x = x.contiguous(memory_format=torch.channels_last)
+    leaves = [t.detach().requires_grad_(True) for t in (x, off, w, b)]
+    out = dc.deform_conv2d(*leaves, **case.conf)
     torch.cuda.synchronize()
-    assert dc.last_kernel() == want_kernel
-    _, gi, go, gw, gb = with_grads(x, off, w, b, gout, padding=1)
-    # bounds with |.| operands: the same gradients of sum(|gout| * out(|x|, |w|)) are sums of non-negative terms
-    _, bi, _, bw, _ = with_grads(x.abs(), off, w.abs(), b, gout.abs(), padding=1)
-    reach = 2 * (H + W + 2 * float(off.abs().max()) + 2 * k)
-    xmax = float(x.abs().max())
-    gcol_abs = torch.einsum("okt,bohw->bkthw", w.double().abs().reshape(Co, C, k * k), gout.double().abs())
-    # grad_input: a K = C_out chain per g_col, <= 4 k^2 corner contributions per element, each corner weight off by the
-    # rounded position
-    checks = [("input", leaves[0].grad, gi, (Co + 16) * bi.abs().max() + reach * 4 * k * k * gcol_abs.max()),
-              ("weight", leaves[2].grad, gw, (H * W * x.shape[0] + 8) * bw.abs().max() + reach * xmax * float(gout.abs().sum())),
-              ("bias", leaves[3].grad, gb, H * W * x.shape[0] * gout.abs().max())]
-    # offset gradient: sum over C of g_col * d sample / d pos, |g_col| <= sum_o |w| |gout|, |d sample / d pos| <= 2 max|x|
-    boff = 2 * xmax * gcol_abs.sum(1).max()
-    mask = _smooth_mask(off, k, H, W)
-    got_off = leaves[1].grad.cpu().double()
-    for d in (0, 1):
-        checks.append((f"offset[{d}]", got_off[:, d::2][mask], go[:, d::2][mask], (Co + C + 16 + reach) * boff))
-    for name, got, want, bound in checks:
-        err = (got.cpu().double() - want).abs().max().item()
-        assert err <= EPS32 * float(bound), (name, err, EPS32 * float(bound))
-        assert want.abs().max().item() > 0, name
+    assert dc.last_kernel() == f"dc_fwd_{route}"
+    out.backward(gout)
+    torch.cuda.synchronize()
+    assert dc.last_kernel() == f"dc_bwd_{route}"
+    return (out.detach(),) + tuple(t.grad for t in leaves)
+
+
+def _matrix_check(name, kind, dtype, cl, route):
+    case = cases.by_name(name)
+    inputs, want, bar = matrix_reference(name, kind)
+    mask = cases.tap_mask_to_channels(cases.smooth_mask(case, inputs[1])) if kind == "random" else None
+    got = _run(case, inputs, dtype, cl, route)
+    check_against_oracle(f"{route} {'cl' if cl else 'nchw'} {kind} {name}", got, want, bar, dtype, mask)
+
+
+@pytest.mark.parametrize("name", [c.name for c in cases.MFMA_CASES])
+def test_matrix_mfma_route_channel_last(name):
+    _matrix_check(name, "random", torch.float32, True, "mfma")
+
+
+@pytest.mark.parametrize("name", ["k3_default", "k5x3_aniso", "k3_s2_rem_c16", "k3_d2_c160", "k3_s2_tiny"])
+def test_matrix_mfma_route_nchw_input_is_transposed_first(name):
+    _matrix_check(name, "random", torch.float32, False, "mfma")
+
+
+@pytest.mark.parametrize("cl", [False, True], ids=["nchw", "cl"])
+@pytest.mark.parametrize("name", [c.name for c in cases.GENERIC_CASES])
+def test_matrix_generic_route_fp32_twins(name, cl):
+    _matrix_check(name, "random", torch.float32, cl, "generic")
+
+
+@pytest.mark.parametrize("name,cl", [(c.name, i % 2 == 1) for i, c in enumerate(cases.MATRIX)],
+                         ids=[f"{c.name}-{'cl' if i % 2 else 'nchw'}" for i, c in enumerate(cases.MATRIX)])
+def test_matrix_generic_route_fp64(name, cl):
+    """fp64 takes the generic kernels on every shape, the MFMA cases' included; the layout alternates over the matrix."""
+    _matrix_check(name, "random", torch.float64, cl, "generic")
+
+
+@pytest.mark.parametrize("name", [c.name for c in cases.DYADIC_CASES])
+def test_dyadic_offsets_without_a_mask_on_both_routes(name):
+    case = cases.by_name(name)
+    on_integer, on_minus_one, on_far_edge = cases.on_grid(case, matrix_reference(name, "dyadic")[0][1])
+    assert on_integer > 0 and on_minus_one > 0 and on_far_edge > 0
+    _matrix_check(name, "dyadic", torch.float32, True, "generic" if "generic" in name else "mfma")
+
+
+@pytest.mark.parametrize("name", NONFINITE_IDS)
+def test_nonfinite_and_huge_offsets_sample_zero_on_both_routes(name):
+    """NaN, +-inf and +-1e9 offsets: dc_foot forms no index before its `in` guard, so such a tap samples 0, the result is
+    finite and equals the oracle's with the tap far outside, and the tap's offset gradient is 0."""
+    case = cases.by_name(name)
+    route = "generic" if "generic" in name else "mfma"
+    got = _run(case, nonfinite_reference(name)[0], torch.float32, True, route)
+    check_nonfinite(f"{route} nonfinite {name}", got, name, torch.float32)
 
 
 def test_gradients_mfma_route():
