@@ -475,6 +475,47 @@ int mvdetr_reg_l1_loss_backward_f64(void *stream, const mvdetr_l1_segment *segs,
 const char *mvdetr_loss_last_kernel(void);
 int64_t mvdetr_loss_launch_count(void);
 
+/* ---- Detection extraction: world heat map -> ground-plane detections ------------------------------------------------
+ * (csrc/detect.hip; additive entries, the ABI version above is unchanged.)  The last stage of the reference's test loop on
+ * the device, without a host round-trip: mvdet_decode (utils/decode.py:80-93), the cls_thres test (trainer.py:130-132) and
+ * the greedy distance NMS (utils/nms.py:7-44).  Per frame b of heatmap [batch, 1, height, width] (raw logits) and offset
+ * [batch, 2, height, width] (NULL: every cell's centre, +0.5), both addressed through their four element strides (host
+ * arrays), so channels_last maps are read in place:
+ *   score  s = 1 / (1 + exp(-logit)); a cell is a candidate when s > cls_thres (rounded to the element type; NaN never is);
+ *   position  x = (column + dx) * reduce, y = (row + dy) * reduce, one rounded add and one rounded multiply; swap_xy != 0
+ *          exchanges them (the reference's indexing = 'ij', trainer.py:125-128);
+ *   NMS    candidates are visited in descending score order, EQUAL SCORES HIGHER ROW-MAJOR CELL INDEX FIRST (the reference's
+ *          order among ties is that of an unstable torch.sort; on tie-free input the two agree); only the first top_k in
+ *          that order take part (top_k <= 0: all); one is kept unless an already kept one lies within
+ *          sqrt(dx * dx + dy * dy) <= dist_thres (rounded to the element type; products and sum rounded separately).
+ * Outputs, all device memory: det [batch, max_det, 3] = (x, y, score) rows in kept order, cell [batch, max_det] the cells'
+ * row-major indices, count [batch] the TRUE number kept, also when it exceeds max_det (rows beyond max_det are dropped,
+ * never written); rows at and after min(count, max_det) are zero.  Correct for any number of candidates up to
+ * height * width (<= 2^30).  workspace: mvdetr_detect_workspace_bytes(batch, height, width, elem_size) bytes, 16-byte aligned,
+ * contents arbitrary.  Two launches ("detect_compact+detect_nms"), no host synchronisation, no floating-point atomics:
+ * bit-reproducible.  The candidate list lives in LDS up to 3072 (f32) / 1728 (f64) candidates of a frame and in the
+ * workspace beyond; MVDETR_DETECT_ROUTE=global keeps it in the workspace always ("..._global").
+ * mvdetr_distance_nms_*: the NMS stage alone, the contract of utils/nms.py:7-44 -- points [n, 2] and scores [n] dense ->
+ * keep [n] int64 (the kept indices, then zeros) and count [1]; workspace of mvdetr_detect_workspace_bytes(1, 1, n, elem_size)
+ * bytes; one launch ("distance_nms" / "distance_nms_global"); n >= 1. */
+int64_t mvdetr_detect_workspace_bytes(int batch, int height, int width, int elem_size);
+int mvdetr_detect_forward_f32(void *stream, const float *heatmap, const int64_t *heatmap_stride, const float *offset,
+                              const int64_t *offset_stride, int batch, int height, int width, double reduce, double cls_thres,
+                              double dist_thres, int top_k, int swap_xy, int max_det, void *workspace, float *det, int32_t *cell,
+                              int32_t *count);
+int mvdetr_detect_forward_f64(void *stream, const double *heatmap, const int64_t *heatmap_stride, const double *offset,
+                              const int64_t *offset_stride, int batch, int height, int width, double reduce, double cls_thres,
+                              double dist_thres, int top_k, int swap_xy, int max_det, void *workspace, double *det, int32_t *cell,
+                              int32_t *count);
+int mvdetr_distance_nms_f32(void *stream, const float *points, const float *scores, int n, double dist_thres, int top_k,
+                            void *workspace, int64_t *keep, int32_t *count);
+int mvdetr_distance_nms_f64(void *stream, const double *points, const double *scores, int n, double dist_thres, int top_k,
+                            void *workspace, int64_t *keep, int32_t *count);
+/* Name of the route the last device detect / NMS call of this process took ("none" before the first), and the number of
+ * kernel launches these entries have made. */
+const char *mvdetr_detect_last_kernel(void);
+int64_t mvdetr_detect_launch_count(void);
+
 /* ---- CPU path (host pointers, no stream, synchronous) ------------------------------------------------------------
  * The reference extension raises for CPU tensors (ms_deform_attn_cpu.cpp:17-41 are stubs; ms_deform_attn.h:38,60).
  * These entry points make the same contracts work on host memory: same argument meaning and layouts as the device
@@ -543,6 +584,20 @@ int mvdetr_attention_backward_host_f64(const double *grad_out, const double *q, 
                                        int sq, int sk, int head_dim, double dropout_p, uint64_t seed, double *grad_q,
                                        double *grad_k, double *grad_v);
 int mvdetr_attention_dropout_mask_host(uint64_t seed, double dropout_p, int batch, int heads, int sq, int sk, uint8_t *mask);
+
+/* detection extraction on host memory: same arguments as the device entries without the stream and the workspace, the same
+ * arithmetic and tie rule; one thread per frame */
+int mvdetr_detect_forward_host_f32(const float *heatmap, const int64_t *heatmap_stride, const float *offset,
+                                   const int64_t *offset_stride, int batch, int height, int width, double reduce, double cls_thres,
+                                   double dist_thres, int top_k, int swap_xy, int max_det, float *det, int32_t *cell, int32_t *count);
+int mvdetr_detect_forward_host_f64(const double *heatmap, const int64_t *heatmap_stride, const double *offset,
+                                   const int64_t *offset_stride, int batch, int height, int width, double reduce, double cls_thres,
+                                   double dist_thres, int top_k, int swap_xy, int max_det, double *det, int32_t *cell,
+                                   int32_t *count);
+int mvdetr_distance_nms_host_f32(const float *points, const float *scores, int n, double dist_thres, int top_k, int64_t *keep,
+                                 int32_t *count);
+int mvdetr_distance_nms_host_f64(const double *points, const double *scores, int n, double dist_thres, int top_k, int64_t *keep,
+                                 int32_t *count);
 
 #ifdef __cplusplus
 }

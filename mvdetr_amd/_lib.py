@@ -50,6 +50,8 @@ class L1Segment(ctypes.Structure):
 
 
 LOSS_MAX_SEGMENTS = 4
+_DETECT = [_vp, _vp, _i64p, _vp, _i64p] + [_i] * 3 + [_d] * 3 + [_i] * 3 + [_vp] * 4
+_NMS = [_vp] * 3 + [_i, _d, _i] + [_vp] * 3
 _FSEG, _LSEG = ctypes.POINTER(FocalSegment), ctypes.POINTER(L1Segment)
 
 SIGNATURES = {
@@ -134,6 +136,17 @@ SIGNATURES = {
     "mvdetr_reg_l1_loss_backward_f64": ([_vp, _LSEG, _i, _vp, _vp], _i),
     "mvdetr_loss_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_loss_launch_count": ([], ctypes.c_int64),
+    "mvdetr_detect_workspace_bytes": ([_i] * 4, ctypes.c_int64),
+    "mvdetr_detect_forward_f32": (_DETECT, _i),
+    "mvdetr_detect_forward_f64": (_DETECT, _i),
+    "mvdetr_distance_nms_f32": (_NMS, _i),
+    "mvdetr_distance_nms_f64": (_NMS, _i),
+    "mvdetr_detect_forward_host_f32": (_DETECT[1:15] + _DETECT[16:], _i),
+    "mvdetr_detect_forward_host_f64": (_DETECT[1:15] + _DETECT[16:], _i),
+    "mvdetr_distance_nms_host_f32": (_NMS[1:6] + _NMS[7:], _i),
+    "mvdetr_distance_nms_host_f64": (_NMS[1:6] + _NMS[7:], _i),
+    "mvdetr_detect_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_detect_launch_count": ([], ctypes.c_int64),
 }
 
 

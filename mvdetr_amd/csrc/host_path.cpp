@@ -746,3 +746,111 @@ MVDETR_ATTN_HOST_ENTRIES(float, f32)
 MVDETR_ATTN_HOST_ENTRIES(double, f64)
 
 }  // extern "C"
+
+// ---- detection extraction (csrc/detect.hip's contract on host memory) ------------------------------------------------------------------
+// The reference's mvdet_decode -> cls_thres -> nms (utils/decode.py:80-93, trainer.py:130-135, utils/nms.py:7-44), one thread per frame:
+// the candidates are sorted once by (score, index) descending -- equal scores: higher index first, the library's tie rule -- cut to the
+// first top_k and swept greedily against the kept points.  Sum and products of the squared distance are separate roundings (this file is
+// compiled for baseline x86-64: no fused multiply-add exists to contract them into).
+namespace {
+
+template <typename T> struct DetCand {
+    T score, x, y;
+    int idx;
+};
+
+template <typename T> int nms_host(std::vector<DetCand<T>> &c, T dist_thres, int top_k, std::vector<int> &kept)
+{
+    std::sort(c.begin(), c.end(), [](const DetCand<T> &a, const DetCand<T> &b) { return a.score > b.score || (a.score == b.score && a.idx > b.idx); });
+    if (top_k > 0 && (size_t)top_k < c.size()) c.resize(top_k);
+    kept.clear();
+    for (size_t j = 0; j < c.size(); ++j) {
+        bool keep = true;
+        for (int k : kept) {
+            const T dx = c[k].x - c[j].x, dy = c[k].y - c[j].y;
+            const T xx = dx * dx, yy = dy * dy;
+            if (!(std::sqrt(xx + yy) > dist_thres)) {
+                keep = false;
+                break;
+            }
+        }
+        if (keep) kept.push_back((int)j);
+    }
+    return (int)kept.size();
+}
+
+template <typename T>
+int detect_host(const T *hm, const int64_t *hs, const T *off, const int64_t *os, int B, int H, int W, double reduce, double cls_thres,
+                double dist_thres, int top_k, int swap_xy, int max_det, T *det, int32_t *cell, int32_t *count)
+{
+    if (!hm || !hs || (off && !os) || !det || !cell || !count || B < 1 || H < 1 || W < 1 || max_det < 1 || (int64_t)H * W > ((int64_t)1 << 30))
+        return 1;
+    const T red = T(reduce), thres = T(cls_thres), dist = T(dist_thres);
+    parallel_ranges(B, [=](int64_t b0, int64_t b1) {
+        std::vector<DetCand<T>> cand;
+        std::vector<int> kept;
+        for (int64_t b = b0; b < b1; ++b) {
+            cand.clear();
+            for (int row = 0; row < H; ++row)
+                for (int col = 0; col < W; ++col) {
+                    const T s = T(1) / (T(1) + std::exp(-hm[b * hs[0] + row * hs[2] + col * hs[3]]));
+                    if (!(s > thres)) continue;
+                    T dx = T(0.5), dy = T(0.5);
+                    if (off) {
+                        const T *o = off + b * os[0] + row * os[2] + col * os[3];
+                        dx = o[0];
+                        dy = o[os[1]];
+                    }
+                    const T x = (T(col) + dx) * red, y = (T(row) + dy) * red;
+                    cand.push_back(DetCand<T>{s + T(0), swap_xy ? y : x, swap_xy ? x : y, row * W + col});
+                }
+            const int n = nms_host(cand, dist, top_k, kept);
+            count[b] = n;
+            T *d = det + b * max_det * 3;
+            int32_t *c = cell + b * max_det;
+            for (int r = 0; r < max_det; ++r) {
+                const bool on = r < n;
+                const DetCand<T> *p = on ? &cand[kept[r]] : nullptr;
+                d[3 * r] = on ? p->x : T(0);
+                d[3 * r + 1] = on ? p->y : T(0);
+                d[3 * r + 2] = on ? p->score : T(0);
+                c[r] = on ? p->idx : 0;
+            }
+        }
+    });
+    return 0;
+}
+
+template <typename T> int distance_nms_host(const T *points, const T *scores, int n, double dist_thres, int top_k, int64_t *keep, int32_t *count)
+{
+    if (!points || !scores || !keep || !count || n < 1) return 1;
+    std::vector<DetCand<T>> cand(n);
+    for (int j = 0; j < n; ++j) cand[j] = DetCand<T>{scores[j] + T(0), points[2 * (int64_t)j], points[2 * (int64_t)j + 1], j};
+    std::vector<int> kept;
+    const int m = nms_host(cand, T(dist_thres), top_k, kept);
+    for (int r = 0; r < n; ++r) keep[r] = r < m ? cand[kept[r]].idx : 0;
+    count[0] = m;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+#define MVDETR_DETECT_HOST_ENTRIES(T, SFX)                                                                                       \
+    int mvdetr_detect_forward_host_##SFX(const T *heatmap, const int64_t *heatmap_stride, const T *offset, const int64_t *offset_stride, \
+                                         int batch, int height, int width, double reduce, double cls_thres, double dist_thres,  \
+                                         int top_k, int swap_xy, int max_det, T *det, int32_t *cell, int32_t *count)             \
+    {                                                                                                                           \
+        return detect_host<T>(heatmap, heatmap_stride, offset, offset_stride, batch, height, width, reduce, cls_thres,           \
+                              dist_thres, top_k, swap_xy, max_det, det, cell, count);                                            \
+    }                                                                                                                           \
+    int mvdetr_distance_nms_host_##SFX(const T *points, const T *scores, int n, double dist_thres, int top_k, int64_t *keep,      \
+                                       int32_t *count)                                                                           \
+    {                                                                                                                           \
+        return distance_nms_host<T>(points, scores, n, dist_thres, top_k, keep, count);                                          \
+    }
+MVDETR_DETECT_HOST_ENTRIES(float, f32)
+MVDETR_DETECT_HOST_ENTRIES(double, f64)
+
+}  // extern "C"

@@ -18,6 +18,7 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
+from .ops.detect import bev_detect
 from .ops.trunk_epilogue import bn_act, bn_relu_maxpool, fused_bn_act_available, fused_bn_relu_maxpool_available
 from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat, TransformerWorldFeat
 
@@ -290,6 +291,17 @@ class MVDeTr(nn.Module):
         world = world.view(B, N, H, W, C) if nhwc else world.view(B, N, C, H, W)
         world = self.world_feat(world)
         return (self.world_heatmap(world), self.world_offset(world)), (imgs_heatmap, imgs_offset, imgs_wh)
+
+    def detect(self, imgs, M, **detect_kw):
+        """Inference down to ground-plane detections: ``forward`` under ``no_grad``, then the fused decode + threshold + distance
+        NMS (ops/detect.py, the tail of the reference's test loop, trainer.py:121-135) on the world head's outputs where they
+        live.  ``detect_kw`` are ``bev_detect``'s (cls_thres, dist_thres, top_k, indexing, max_det); ``world_reduce`` defaults to
+        the geometry's.  Returns ``bev_detect``'s result object, all on the device: nothing here waits for the GPU.  The forward
+        goes through ``__call__``, so a forward hook on the model sees the very maps the detections come from."""
+        with torch.no_grad():
+            (world_heatmap, world_offset), _ = self(imgs, M)
+        detect_kw.setdefault("world_reduce", self.geom.world_reduce)
+        return bev_detect(world_heatmap, world_offset, **detect_kw)
 
     def hot_path(self, feat, proj):
         """warp + shadow transformer only (the path BASELINE.json's north_star names), for timing."""

@@ -16,3 +16,4 @@ from .add_layernorm import add_layer_norm  # noqa: E402,F401
 from .trunk_epilogue import bn_act, bn_relu_maxpool, set_trunk_fusion  # noqa: E402,F401
 from .deform_conv import deform_conv2d, DeformConv2d, DeformConv2dFunction  # noqa: E402,F401
 from .attention import attention, MultiheadAttention, AttentionFunction  # noqa: E402,F401
+from .detect import bev_detect, distance_nms, Detections  # noqa: E402,F401
