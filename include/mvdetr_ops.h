@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 16   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load) */
+#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -298,6 +298,10 @@ int64_t mvdetr_trunk_launch_count(void);
 const char *mvdetr_msda_last_forward_impl(void);
 /* Name of the kernel that call launched ("msda_fwd_group[LDS-DMA windows]", "msda_fwd_tile", "msda_fwd_gather", ...). */
 const char *mvdetr_msda_last_forward_kernel(void);
+/* Name of the route the last MSDA backward ON THIS THREAD took through either entry ("twopass", "split", "onepass", "atomic",
+ * "deterministic", "fused-split", "fused-twopass", "fused-onepass", "fused-groups", "fused-deterministic"; "none" before the
+ * first).  An empty or refused call leaves it as it was.  Static storage; never NULL. */
+const char *mvdetr_msda_last_backward_route(void);
 
 /* What the code object records for that kernel instantiation (hipFuncGetAttributes): registers per lane, scratch bytes per
  * lane (non-zero = the instantiation spills), static LDS bytes.  Returns 0 (and -1 in the outputs) when unknown. */

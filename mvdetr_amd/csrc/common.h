@@ -150,6 +150,35 @@ template <typename T> struct PerDevice {
     }
 };
 
+// Workgroups of a persistent launch, computed once per device: sets the kernel's dynamic-LDS attribute, then CU count x workgroups
+// per CU -- what the occupancy query admits for `threads` and `lds` bytes (`fallback` when it fails, at most `cap`), or, with
+// threads == 0, `fallback` as a fixed count -- rounded up to a multiple of 8 to keep the XCD interleave whole.  `report` sees
+// the workgroups per CU (the MVDETR_DEBUG_OCCUPANCY prints).
+struct PersistentGrid {
+    PerDevice<int> blocks_of;
+    template <typename Kernel>
+    int blocks(Kernel kernel, int lds_attr, int threads, int lds, int fallback, int cap = 1 << 20, void (*report)(int) = nullptr)
+    {
+        return blocks_of.get([=] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr);
+            int dev = 0, cus = 256, per_cu = 0;
+            if (hipGetDevice(&dev) != hipSuccess ||
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+                cus = 256;
+            if (!threads || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1)
+                per_cu = fallback;
+            if (per_cu > cap) per_cu = cap;
+            if (report) report(per_cu);
+            return (cus * per_cu + 7) / 8 * 8;
+        });
+    }
+    template <typename Kernel> int occupancy(Kernel kernel, int threads, int lds, int fallback, int cap = 1 << 20, void (*report)(int) = nullptr)
+    {
+        return blocks(kernel, lds, threads, lds, fallback, cap, report);
+    }
+    template <typename Kernel> int fixed(Kernel kernel, int lds_attr, int per_cu) { return blocks(kernel, lds_attr, 0, 0, per_cu); }
+};
+
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }

@@ -14,8 +14,8 @@
 // grad_value is accumulated with hardware fp atomics (global_atomic_add_f32/f64,
 // -munsafe-fp-atomics), i.e. the summation order -- like the reference's atomicAdd
 // (cuh:125-152) -- is not deterministic.
-// Encoder-shaped fp32 calls do not end up here: backward_entry() sends them to msda_backward_tile.hip
-// (grad_value, fixed-point LDS windows) + msda_backward_sampling.hip (the other two gradients).
+// Encoder-shaped fp32 calls do not end up here: msda_backward_route.h sends them to the LDS-window kernels
+// (msda_backward_value_tok.hip / msda_backward_onepass.hip / msda_backward_sampling.hip / msda_backward_fused.hip).
 #include "common.h"
 #include "msda_dispatch.h"
 #include "msda_backward_lanes.h"
@@ -112,96 +112,106 @@ static int launch_lanes(hipStream_t st, const T *grad_col, const T *value, const
     return (int)hipGetLastError();
 }
 
+// msda_bwd_lanes<T, VEC, g> for g = 1, 2, .. 64
+template <typename T, int VEC>
+static int launch_lanes_g(int g, hipStream_t st, const T *grad_col, const T *value, const int64_t *shapes,
+                          const int64_t *lsi, const T *loc, const T *aw, int B, int S, int M, int D, int L,
+                          int Lq, int P, T *grad_value, T *grad_loc, T *grad_aw)
+{
+    switch (g) {
+    case 1: return launch_lanes<T, VEC, 1>(st, MSDA_BWD_ARGS);
+    case 2: return launch_lanes<T, VEC, 2>(st, MSDA_BWD_ARGS);
+    case 4: return launch_lanes<T, VEC, 4>(st, MSDA_BWD_ARGS);
+    case 8: return launch_lanes<T, VEC, 8>(st, MSDA_BWD_ARGS);
+    case 16: return launch_lanes<T, VEC, 16>(st, MSDA_BWD_ARGS);
+    case 32: return launch_lanes<T, VEC, 32>(st, MSDA_BWD_ARGS);
+    case 64: return launch_lanes<T, VEC, 64>(st, MSDA_BWD_ARGS);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+// MVDETR_MSDA_BWD_IMPL, read once (msda_backward_route.h says what each setting runs through either entry)
+static MsdaBwdKnob backward_knob()
+{
+    static const MsdaBwdKnob knob = msda_backward_parse_knob(getenv("MVDETR_MSDA_BWD_IMPL"));
+    return knob;
+}
+
+static thread_local MsdaBwdKind g_last_bwd_route = MsdaBwdKind::none;
+
+// true: the call ends here with `rc` (success for an empty call, else the refusal); false: run the route, now on record
+static bool route_refused(const MsdaBwdRoute &r, bool null_pointer, int &rc)
+{
+    rc = 0;
+    if (r.status == MsdaBwdStatus::empty) return true;
+    if (r.status == MsdaBwdStatus::invalid_value || null_pointer) rc = (int)hipErrorInvalidValue;
+    else if (r.status == MsdaBwdStatus::not_supported) rc = (int)hipErrorNotSupported;
+    if (!rc) g_last_bwd_route = r.kind;
+    return rc != 0;
+}
+
+// the LDS-window routes of both entries
+static int run_route(const MsdaBwdRoute &r, const MsdaBwdCall &c)
+{
+    int rc;
+    switch (r.kind) {
+    case MsdaBwdKind::twopass: {
+        // a stream-ordered scratch carries the locality probe's verdict to both kernels: calls whose taps are far from their
+        // queries (e.g. uniformly random locations) run the lane-group backward inside the first launch instead -- no host
+        // synchronisation.  (No probe means something else to the sampling kernels -- "take your own sample and skip the tiles
+        // the grad_value kernel has taken along" -- and this route's grad_value kernel never takes a tile along: an allocation
+        // failure is returned, not papered over.)
+        int *hits = nullptr;
+        const hipError_t arc = hipMallocAsync(reinterpret_cast<void **>(&hits), MSDA_PROBE_INTS * sizeof(int), c.st);
+        if (arc != hipSuccess || !hits) return (int)(arc != hipSuccess ? arc : hipErrorOutOfMemory);
+        rc = msda_launch_locality_probe(c.st, c.loc, c.shapes, c.B, c.S, c.M, c.L, hits);
+        if (!rc) rc = msda_backward_value_tok(c, hits);
+        if (!rc) rc = msda_backward_sampling(c, r.sampling, hits);
+        (void)hipFreeAsync(hits, c.st);
+        return rc;
+    }
+    case MsdaBwdKind::split:
+        // no probe, no scratch: both kernels take the window shift and the stand-down decision from their jobs' own samples
+        rc = msda_backward_scatter(c, 1);
+        return rc ? rc : msda_backward_sampling(c, r.sampling, nullptr);
+    case MsdaBwdKind::onepass: return msda_backward_onepass(c, 1);
+    case MsdaBwdKind::fused_onepass: return msda_backward_onepass(c, 0);
+    case MsdaBwdKind::deterministic:
+    case MsdaBwdKind::fused_deterministic: return msda_backward_deterministic(c);
+    case MsdaBwdKind::fused_split:
+        rc = msda_backward_scatter(c, 0);
+        return rc ? rc : msda_backward_fused_sampling(c);
+    case MsdaBwdKind::fused_twopass:
+        rc = msda_backward_value_tok(c, nullptr);
+        return rc ? rc : msda_backward_fused_sampling(c);
+    case MsdaBwdKind::fused_groups:
+        rc = msda_backward_value_tok(c, nullptr);
+        return rc ? rc : msda_backward_sampling(c, r.sampling, nullptr);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
 template <typename T>
 static int backward_entry(void *stream, const T *grad_col, const T *value, const int64_t *shapes,
                           const int64_t *lsi, const T *loc, const T *aw, int B, int S, int M, int D, int L,
                           int Lq, int P, T *grad_value, T *grad_loc, T *grad_aw)
 {
-    if (B < 0 || S < 0 || M <= 0 || D <= 0 || L <= 0 || Lq < 0 || P <= 0) return (int)hipErrorInvalidValue;
-    if ((int64_t)B * Lq == 0) return 0;
-    if (!grad_col || !value || !shapes || !lsi || !loc || !aw || !grad_value || !grad_loc || !grad_aw)
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    constexpr int WIDE = 16 / (int)sizeof(T);
     const bool a16 = aligned(value, 16) && aligned(grad_col, 16);
-    if (sizeof(T) != 4 && backward_deterministic().load(std::memory_order_relaxed)) return (int)hipErrorNotSupported;
+    const bool all16 = a16 && aligned(loc, 16) && aligned(aw, 16) && aligned(grad_value, 16) && aligned(grad_loc, 16) &&
+                       aligned(grad_aw, 16);
+    const MsdaBwdRoute r = msda_backward_route(sizeof(T) == 4 ? MsdaBwdEntry::public_f32 : MsdaBwdEntry::public_f64, B, S, M, D, L, Lq, P, 0,
+                                               all16, a16, backward_knob(), backward_deterministic().load(std::memory_order_relaxed) != 0);
+    int rc;
+    if (route_refused(r, !grad_col || !value || !shapes || !lsi || !loc || !aw || !grad_value || !grad_loc || !grad_aw, rc)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if constexpr (sizeof(T) == 4) {
-        // Encoder-shaped fp32 calls (the shapes the forward tile kernels take): grad_value through fixed-point LDS
-        // windows (msda_backward_tile.hip), the other two gradients from LDS-staged value windows (msda_backward_sampling.hip).
-        // MVDETR_MSDA_BWD_IMPL=atomic keeps everything on the direct-atomics kernel.
-        static const bool tile_ok = [] { const char *e = getenv("MVDETR_MSDA_BWD_IMPL"); return !(e && !strcmp(e, "atomic")); }();
-        const bool all16 = a16 && aligned(loc, 16) && aligned(aw, 16) && aligned(grad_value, 16) && aligned(grad_loc, 16) &&
-                           aligned(grad_aw, 16);
-        // MVDETR_MSDA_BWD_IMPL = twopass (default of this entry: msda_locality_probe + msda_bwd_value_tok + msda_bwd_sampling_*) |
-        // split (grad_value from msda_bwd_onepass<DOTS = 0>, no probe launch; the default of the FUSED entry below) | onepass (all
-        // three gradients from ONE kernel, msda_backward_onepass.hip) | atomic (the generic kernel).
-        // The default is the measured one (profiles/r06_bwd_ab.txt, same box, realistic / uniform input): Wildtrack 625 / 3,383 us
-        // twopass, 642 / 3,607 split, 671 / 3,960 onepass; MultiviewX 458 / 2,316, 458 / 2,360, 506 / 2,527 -- round 5 had made
-        // `split` the default to save the 6-us probe launch; it moves 2.4 x the bytes and is not faster.
-        static const int impl = [] {
-            const char *e = getenv("MVDETR_MSDA_BWD_IMPL");
-            return !e ? 2 : !strcmp(e, "onepass") ? 1 : !strcmp(e, "split") ? 0 : 2;
-        }();
-        const bool tile_shapes = tile_ok && msda_tile_supported(B, S, M, D, L, Lq, P, all16, 0, L);
-        const bool op_ok = tile_shapes && msda_backward_onepass_supported(B, S, M, D, L, (int64_t)M * L * P * 2);
-        if (backward_deterministic().load(std::memory_order_relaxed)) {
-            // one kernel does it (msda_bwd_onepass<DET>); calls it does not take are refused, not served by a kernel that is not
-            if (!tile_shapes || !msda_backward_deterministic_supported(B, S, M, D, L, (int64_t)M * L * P * 2)) return (int)hipErrorNotSupported;
-            return msda_backward_onepass_det(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_value, grad_loc, grad_aw);
-        }
-        if (op_ok && impl == 1)
-            return msda_backward_onepass(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_value, grad_loc, grad_aw, true);
-        if (op_ok && impl == 0) {
-            // no probe, no scratch: both kernels take the window shift and the stand-down decision from their jobs' own samples
-            int rc = msda_backward_scatter(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_value, grad_loc, grad_aw, true);
-            if (!rc) rc = msda_backward_sampling_tile(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_loc, grad_aw, nullptr);
-            return rc;
-        }
-        if (tile_shapes && msda_backward_value_tile_fits(S, M, D, L)) {
-            // rounds 2-4's pair (and 32-channel heads): a stream-ordered scratch int carries the locality probe's verdict to both
-            // kernels: calls whose taps are far from their queries (e.g. uniformly random locations) run the lane-group
-            // backward inside the first launch instead -- no host synchronisation
-            // (no probe means something else to the sampling kernels -- "take your own sample and skip the tiles the grad_value
-            // kernel has taken along" -- and this path's grad_value kernel never takes a tile along: an allocation failure is
-            // returned, not papered over)
-            int *hits = nullptr;
-            const hipError_t arc = hipMallocAsync(reinterpret_cast<void **>(&hits), MSDA_PROBE_INTS * sizeof(int), st);
-            if (arc != hipSuccess || !hits) return (int)(arc != hipSuccess ? arc : hipErrorOutOfMemory);
-            int rc = msda_launch_locality_probe(st, loc, shapes, B, S, M, L, hits);
-            if (!rc) rc = msda_backward_value_tile(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_value, grad_loc, grad_aw, hits);
-            if (!rc) rc = msda_backward_sampling_tile(st, grad_col, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_loc, grad_aw, hits);
-            (void)hipFreeAsync(hits, st);
-            return rc;
-        }
+        if (r.kind != MsdaBwdKind::atomic)
+            return run_route(r, MsdaBwdCall{st, grad_col, value, shapes, lsi, loc, aw, nullptr, 0, 0, nullptr, false, B, S, M, D, L,
+                                            grad_value, grad_loc, grad_aw});
     }
-    // One channel per lane (G = D lanes per head): a wave's atomic instruction then covers whole
-    // 4*D-byte head segments, which the memory-side atomic units take as ONE request each, instead of four
-    // partial ones with 16-byte-per-lane vectors (measured at Wildtrack size: 3.15 ms vs 12.7 ms -- the
-    // kernel is bound by atomic requests, ~21 G/s, not by bytes).
-    if (D <= 64 && (D & (D - 1)) == 0) {
-        switch (D) {
-        case 1: return launch_lanes<T, 1, 1>(st, MSDA_BWD_ARGS);
-        case 2: return launch_lanes<T, 1, 2>(st, MSDA_BWD_ARGS);
-        case 4: return launch_lanes<T, 1, 4>(st, MSDA_BWD_ARGS);
-        case 8: return launch_lanes<T, 1, 8>(st, MSDA_BWD_ARGS);
-        case 16: return launch_lanes<T, 1, 16>(st, MSDA_BWD_ARGS);
-        case 32: return launch_lanes<T, 1, 32>(st, MSDA_BWD_ARGS);
-        case 64: return launch_lanes<T, 1, 64>(st, MSDA_BWD_ARGS);
-        default: break;
-        }
-    }
-    if (a16 && D % WIDE == 0) {
-        switch (D / WIDE) {
-        case 1: return launch_lanes<T, WIDE, 1>(st, MSDA_BWD_ARGS);
-        case 2: return launch_lanes<T, WIDE, 2>(st, MSDA_BWD_ARGS);
-        case 4: return launch_lanes<T, WIDE, 4>(st, MSDA_BWD_ARGS);
-        case 8: return launch_lanes<T, WIDE, 8>(st, MSDA_BWD_ARGS);
-        case 16: return launch_lanes<T, WIDE, 16>(st, MSDA_BWD_ARGS);
-        case 32: return launch_lanes<T, WIDE, 32>(st, MSDA_BWD_ARGS);
-        case 64: return launch_lanes<T, WIDE, 64>(st, MSDA_BWD_ARGS);
-        default: break;
-        }
-    }
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    if (r.lanes_vec == 1) return launch_lanes_g<T, 1>(r.lanes_g, st, MSDA_BWD_ARGS);
+    if (r.lanes_vec == WIDE) return launch_lanes_g<T, WIDE>(r.lanes_g, st, MSDA_BWD_ARGS);
     const int64_t total = (int64_t)B * Lq * M;
     int64_t blocks = (total + 255) / 256;
     if (blocks > (1 << 20)) blocks = 1 << 20;
@@ -235,6 +245,8 @@ int mvdetr_msda_get_backward_deterministic(void) { return mvdetr::backward_deter
 
 int mvdetr_msda_release_scratch(void) { return mvdetr::msda_release_det_scratch(); }
 
+const char *mvdetr_msda_last_backward_route(void) { return mvdetr::msda_backward_route_name(mvdetr::g_last_bwd_route); }
+
 int mvdetr_msda_backward_fused_f32(void *stream, const float *grad_output, const float *value,
                                    const int64_t *spatial_shapes, const int64_t *level_start_index,
                                    const float *reference_points, int64_t ref_batch_stride, const float *raw,
@@ -243,71 +255,18 @@ int mvdetr_msda_backward_fused_f32(void *stream, const float *grad_output, const
                                    float *grad_raw)
 {
     using namespace mvdetr;
-    if (batch < 0 || spatial_size < 0 || num_heads <= 0 || channels <= 0 || num_levels <= 0 || num_point <= 0)
-        return (int)hipErrorInvalidValue;
-    if ((int64_t)batch * spatial_size == 0) return 0;
-    if (!grad_output || !value || !spatial_shapes || !level_start_index || !reference_points || !raw || !stats || !out ||
-        !grad_value || !grad_raw)
-        return (int)hipErrorInvalidValue;
-    if (!mvdetr_msda_fused_train_supported(batch, spatial_size, num_heads, channels, num_levels, spatial_size, num_point))
-        return (int)hipErrorNotSupported;
-    if (raw_query_stride < num_heads * num_levels * num_point * 3 || raw_query_stride % 4) return (int)hipErrorInvalidValue;
-    // the kernels address one batch element's raw tensor (and its gradient) with 32-bit offsets of the CALLER's query stride,
-    // which may be wider than the dense width mvdetr_msda_fused_train_supported() bounds (a column block of a wider GEMM)
-    if ((int64_t)spatial_size * raw_query_stride >= ((int64_t)1 << 29)) return (int)hipErrorNotSupported;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(grad_output) | reinterpret_cast<uintptr_t>(value) |
-                         reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out) |
-                         reinterpret_cast<uintptr_t>(grad_value) | reinterpret_cast<uintptr_t>(grad_raw);
-    if ((al & 15) || (reinterpret_cast<uintptr_t>(reference_points) & 7) || (reinterpret_cast<uintptr_t>(stats) & 7) ||
-        (ref_batch_stride & 1))
-        return (int)hipErrorNotSupported;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // MVDETR_MSDA_BWD_IMPL for this entry: split (default: msda_bwd_onepass<fused, DOTS = 0> + msda_bwd_fused_sampling) | twopass
-    // (msda_bwd_value_tok<fused> for grad_value) | onepass.  Measured (profiles/r06_bwd_ab.txt): Wildtrack 549 us split, 564
-    // twopass, 706 onepass; MultiviewX 386 / 404 / 493.
-    static const int impl = [] {
-        const char *e = getenv("MVDETR_MSDA_BWD_IMPL");
-        return !e ? 0 : !strcmp(e, "onepass") ? 1 : !strcmp(e, "twopass") ? 2 : 0;
-    }();
-    const bool op_ok = msda_backward_onepass_supported(batch, spatial_size, num_heads, channels, num_levels, raw_query_stride);
-    const bool det = backward_deterministic().load(std::memory_order_relaxed) != 0;
-    if (!det && !(channels == 16 && (num_levels == 6 || num_levels == 7))) {
-        // every other encoder shape (ABI 13): 16-channel heads -> the one-pass kernel (any level count); 32-channel heads ->
-        // msda_bwd_value_tok<32, fused> + the level-groups sampling kernel on the raw tensor
-        if (channels == 16 && op_ok)
-            return msda_backward_onepass_fused(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                               reference_points, ref_batch_stride, stats, out, batch, spatial_size, num_heads,
-                                               channels, num_levels, grad_value, grad_raw);
-        int rc = msda_backward_value_tile_fused(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                                reference_points, ref_batch_stride, stats, batch, spatial_size, num_heads, channels,
-                                                num_levels, grad_value);
-        if (rc) return rc;
-        return msda_backward_fused_sampling_groups(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                                   reference_points, ref_batch_stride, stats, out, batch, spatial_size, num_heads,
-                                                   channels, num_levels, grad_raw);
-    }
-    if (det) {
-        if (!msda_backward_deterministic_supported(batch, spatial_size, num_heads, channels, num_levels, raw_query_stride))
-            return (int)hipErrorNotSupported;
-        return msda_backward_onepass_fused_det(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                               reference_points, ref_batch_stride, stats, out, batch, spatial_size, num_heads,
-                                               channels, num_levels, grad_value, grad_raw);
-    }
-    if (op_ok && impl == 1)
-        return msda_backward_onepass_fused(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                           reference_points, ref_batch_stride, stats, out, batch, spatial_size, num_heads,
-                                           channels, num_levels, grad_value, grad_raw);
-    int rc = op_ok && impl == 0
-                 ? msda_backward_scatter_fused(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                               reference_points, ref_batch_stride, stats, batch, spatial_size, num_heads, channels,
-                                               num_levels, grad_value)
-                 : msda_backward_value_tile_fused(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                                  reference_points, ref_batch_stride, stats, batch, spatial_size, num_heads,
-                                                  channels, num_levels, grad_value);
-    if (rc) return rc;
-    return msda_backward_fused_sampling(st, grad_output, value, spatial_shapes, level_start_index, raw, raw_query_stride,
-                                        reference_points, ref_batch_stride, stats, out, batch, spatial_size, num_heads,
-                                        channels, num_levels, grad_raw);
+    const bool all16 = aligned(grad_output, 16) && aligned(value, 16) && aligned(raw, 16) && aligned(out, 16) && aligned(grad_value, 16) &&
+                       aligned(grad_raw, 16) && aligned(reference_points, 8) && aligned(stats, 8) && !(ref_batch_stride & 1);
+    const MsdaBwdRoute r = msda_backward_route(MsdaBwdEntry::fused, batch, spatial_size, num_heads, channels, num_levels, spatial_size,
+                                               num_point, raw_query_stride, all16, all16, backward_knob(),
+                                               backward_deterministic().load(std::memory_order_relaxed) != 0);
+    int rc;
+    if (route_refused(r, !grad_output || !value || !spatial_shapes || !level_start_index || !reference_points || !raw || !stats || !out ||
+                             !grad_value || !grad_raw, rc))
+        return rc;
+    return run_route(r, MsdaBwdCall{reinterpret_cast<hipStream_t>(stream), grad_output, value, spatial_shapes, level_start_index, raw, stats,
+                                    reference_points, ref_batch_stride, raw_query_stride, out, true, batch, spatial_size, num_heads, channels,
+                                    num_levels, grad_value, grad_raw, nullptr});
 }
 
 int mvdetr_msda_backward_f64(void *stream, const double *grad_col, const double *value,

@@ -26,7 +26,7 @@
 // lines, written by four jobs that run at the same time on one XCD.  Taps whose footprint leaves the window read zeros in
 // the stream and are redone from global memory after the level's stream (rare; their stores overwrite the stream's).
 //
-// grad_value comes from msda_bwd_value_win<D, FUSED = 1> (msda_backward_tile.hip), which reads the same raw tensor.
+// grad_value comes from msda_bwd_onepass<fused, DOTS = 0> or msda_bwd_value_tok<D, fused> (msda_backward_route.h), which reads the same raw tensor.
 #include "msda_group2_kernel.h"
 #include "../../include/mvdetr_ops.h"
 
@@ -422,42 +422,26 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void msda_bwd_fused_sampling(
 }
 
 template <typename Cfg, int NG>
-static int launch_bwd_fused_sampling(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                     const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                     const float *stats, const float *out_fwd, int B, int S, int M, float *grad_raw, int opts)
+static int launch_bwd_fused_sampling(const MsdaBwdCall &c, int opts)
 {
 #ifndef MVDETR_FS_DEPTH
 #define MVDETR_FS_DEPTH 2
 #endif
     constexpr int DEPTH = MVDETR_FS_DEPTH;
     constexpr int LDS = Group2Lds<Cfg, NG>::BYTES;
-    auto kernel = &msda_bwd_fused_sampling<Cfg, NG, DEPTH>;
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_fused_sampling<Cfg, NG, DEPTH>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msda_bwd_fused_sampling<Cfg, NG, DEPTH>, Cfg::THREADS, LDS) != hipSuccess || per_cu < 1)
-            per_cu = 2;
-        return (cus * per_cu + 7) / 8 * 8;
-    });
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, st, go, value, shapes, lsi, raw, raw_q, ref,
-                       ref_bstride, stats, out_fwd, B, S, M, grad_raw, opts);
+    static PersistentGrid grid;
+    const int blocks = grid.occupancy(&msda_bwd_fused_sampling<Cfg, NG, DEPTH>, Cfg::THREADS, LDS, 2);
+    hipLaunchKernelGGL((msda_bwd_fused_sampling<Cfg, NG, DEPTH>), dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, c.st, c.go, c.value, c.shapes,
+                       c.lsi, c.loc, c.raw_q, c.ref, c.ref_bstride, c.aw, c.out_fwd, c.B, c.S, c.M, c.grad_loc, opts);
     return (int)hipGetLastError();
 }
 
-int msda_backward_fused_sampling(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                 const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                 const float *stats, const float *out_fwd, int B, int S, int M, int D, int L, float *grad_raw)
+// c.loc / c.aw / c.grad_loc: the raw tensor, the forward's statistics, grad_raw
+int msda_backward_fused_sampling(const MsdaBwdCall &c)
 {
     const int opts = GROUP_OPT_BLOCKS;
-    if (D == 16 && L == 7)
-        return launch_bwd_fused_sampling<GWide16, 7>(st, go, value, shapes, lsi, raw, raw_q, ref, ref_bstride, stats, out_fwd, B, S, M, grad_raw, opts);
-    if (D == 16 && L == 6)
-        return launch_bwd_fused_sampling<GWide16, 6>(st, go, value, shapes, lsi, raw, raw_q, ref, ref_bstride, stats, out_fwd, B, S, M, grad_raw, opts);
+    if (c.D == 16 && c.L == 7) return launch_bwd_fused_sampling<GWide16, 7>(c, opts);
+    if (c.D == 16 && c.L == 6) return launch_bwd_fused_sampling<GWide16, 6>(c, opts);
     return (int)hipErrorNotSupported;
 }
 

@@ -1,5 +1,5 @@
 // Lane-group formulation of the MSDA backward (any shapes / dtypes), shared by msda_backward.hip (its kernel) and
-// msda_backward_tile.hip (in-launch fallback for levels of unequal shape).  Internal, not part of the C ABI.
+// msda_backward_value_tok.hip (in-launch fallback for levels of unequal shape).  Internal, not part of the C ABI.
 #pragma once
 #include "common.h"
 

@@ -38,6 +38,7 @@
 #include <string.h>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #ifndef MVDETR_SCATTER_WGS
@@ -901,70 +902,35 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::WPS) void msda_bwd_onepass(
 }
 
 template <int FUSED, typename Cfg, int NC, bool DET>
-static int launch_onepass_nc(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int L, float *grad_value, float *grad_loc,
-                          float *grad_aw, const float *ref, int64_t ref_bstride, int raw_q, const float *out_fwd, int opts,
-                          long long *det_acc, const unsigned *det_hdr)
+static int launch_onepass_nc(const MsdaBwdCall &c, int opts, long long *det_acc, const unsigned *det_hdr)
 {
     constexpr int LDS = Cfg::LDS;
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_onepass<FUSED, Cfg, NC, DET>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msda_bwd_onepass<FUSED, Cfg, NC, DET>, Cfg::THREADS, LDS) != hipSuccess || per_cu < 1)
-            per_cu = Cfg::WGS;
-        if (per_cu > Cfg::WGS) per_cu = Cfg::WGS;
+    static PersistentGrid grid;
+    const int blocks = grid.occupancy(&msda_bwd_onepass<FUSED, Cfg, NC, DET>, Cfg::THREADS, LDS, Cfg::WGS, Cfg::WGS, [](int per_cu) {
         if (getenv("MVDETR_DEBUG_OCCUPANCY"))
             fprintf(stderr, "msda_bwd_onepass<%d, %dx%d, %d, %d>: %d workgroups per CU (LDS admits %d), %d B of LDS, %d threads\n", FUSED,
                     Cfg::TH, Cfg::TW, NC, (int)DET, per_cu, Cfg::WGS, LDS, Cfg::THREADS);
-        return (cus * per_cu + 7) / 8 * 8;
     });
-    hipLaunchKernelGGL((msda_bwd_onepass<FUSED, Cfg, NC, DET>), dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, st, go, value, shapes, lsi, loc, aw,
-                       B, S, M, L, grad_value, grad_loc, grad_aw, ref, ref_bstride, raw_q, out_fwd, opts, det_acc, det_hdr);
+    hipLaunchKernelGGL((msda_bwd_onepass<FUSED, Cfg, NC, DET>), dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, c.st, c.go, c.value, c.shapes,
+                       c.lsi, c.loc, c.aw, c.B, c.S, c.M, c.L, c.grad_value, c.grad_loc, c.grad_aw, c.ref, c.ref_bstride, c.raw_q, c.out_fwd,
+                       opts, det_acc, det_hdr);
     return (int)hipGetLastError();
 }
 
-template <int FUSED, typename Cfg, bool DET = false>
-static int launch_onepass(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int L, float *grad_value, float *grad_loc,
-                          float *grad_aw, const float *ref, int64_t ref_bstride, int raw_q, const float *out_fwd, int opts,
-                          long long *det_acc = nullptr, const unsigned *det_hdr = nullptr)
+template <typename Cfg, bool DET = false>
+static int launch_onepass(const MsdaBwdCall &c, int opts, long long *det_acc = nullptr, const unsigned *det_hdr = nullptr)
 {
-#define NC_ARGS st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw, ref, ref_bstride, raw_q, out_fwd, opts, det_acc, det_hdr
-    if (L % 7 == 0) return launch_onepass_nc<FUSED, Cfg, 7, DET>(NC_ARGS);
-    if (L % 8 == 0) return launch_onepass_nc<FUSED, Cfg, 8, DET>(NC_ARGS);
-    if (L % 6 == 0) return launch_onepass_nc<FUSED, Cfg, 6, DET>(NC_ARGS);
-    return launch_onepass_nc<FUSED, Cfg, 0, DET>(NC_ARGS);
-#undef NC_ARGS
+    auto nc = [&](auto fused) {
+        constexpr int FUSED = decltype(fused)::value;
+        if (c.L % 7 == 0) return launch_onepass_nc<FUSED, Cfg, 7, DET>(c, opts, det_acc, det_hdr);
+        if (c.L % 8 == 0) return launch_onepass_nc<FUSED, Cfg, 8, DET>(c, opts, det_acc, det_hdr);
+        if (c.L % 6 == 0) return launch_onepass_nc<FUSED, Cfg, 6, DET>(c, opts, det_acc, det_hdr);
+        return launch_onepass_nc<FUSED, Cfg, 0, DET>(c, opts, det_acc, det_hdr);
+    };
+    return !c.fused ? nc(std::integral_constant<int, 0>{}) : nc(std::integral_constant<int, 1>{});
 }
 
-bool msda_backward_onepass_supported(int B, int S, int M, int D, int L, int64_t q_floats)
-{
-    // 16-channel heads; one batch element's tensors addressed with 32-bit byte offsets
-    const int64_t lim = (int64_t)1 << 31;
-    return D == 16 && L <= TILE_MAX_LEVELS && (int64_t)S * M * D * 4 < lim && (int64_t)S * q_floats * 4 < lim;
-}
-
-int msda_backward_onepass(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                          float *grad_loc, float *grad_aw, bool standdown)
-{
-    return launch_onepass<0, OnePassCfg<4, 16, 6, 1>>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw,
-                                                      nullptr, 0, 0, nullptr, standdown ? 1 : 0);
-}
-
-int msda_backward_onepass_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                const float *stats, const float *out_fwd, int B, int S, int M, int D, int L,
-                                float *grad_value, float *grad_raw)
-{
-    return launch_onepass<1, OnePassCfg<4, 16, 6, 1>>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_value, grad_raw, nullptr,
-                                                      ref, ref_bstride, raw_q, out_fwd, 0);
-}
+int msda_backward_onepass(const MsdaBwdCall &c, int opts) { return launch_onepass<OnePassCfg<4, 16, 6, 1>>(c, opts); }
 
 // ---- deterministic mode: the one-pass kernel with 64-bit fixed-point sums for grad_value ------------------------------------
 // (the reference's col2im adds with atomicAdd, cuh:125-152, and is not reproducible run to run; this is the opt-in that is.)
@@ -1005,12 +971,6 @@ __global__ __launch_bounds__(256) void msda_det_finish(const long long *__restri
         const long long v = acc[i];
         if (v) grad_value[i] += (float)ldexp((double)v, -s);
     }
-}
-
-bool msda_backward_deterministic_supported(int B, int S, int M, int D, int L, int64_t q_floats)
-{
-    // (an element's sum stays below 2^38 x the taps that can land on it: 2^24 of them leave a factor two to int64)
-    return msda_backward_onepass_supported(B, S, M, D, L, q_floats) && (int64_t)S * L * TILE_P < ((int64_t)1 << 24);
 }
 
 // the deterministic mode's scratch (header + 8 bytes per value element), kept per (device, stream) between calls and grown on
@@ -1055,50 +1015,29 @@ int msda_release_det_scratch()
     return rc;
 }
 
-template <int FUSED>
-static int onepass_det(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *aw, int B, int S, int M, int L, float *grad_value, float *grad_loc,
-                       float *grad_aw, const float *ref, int64_t ref_bstride, int raw_q, const float *out_fwd)
+int msda_backward_deterministic(const MsdaBwdCall &c)
 {
-    const int64_t n = (int64_t)B * S * M * 16;
+    const int64_t n = (int64_t)c.B * c.S * c.M * 16;
     if (n == 0) return 0;
     const size_t bytes = DET_HDR_BYTES + (size_t)n * sizeof(long long);
     int rc = 0;
-    char *scratch = det_scratch(st, bytes, rc);
+    char *scratch = det_scratch(c.st, bytes, rc);
     if (!scratch) return rc ? rc : (int)hipErrorOutOfMemory;
     unsigned *hdr = reinterpret_cast<unsigned *>(scratch);
     long long *acc = reinterpret_cast<long long *>(scratch + DET_HDR_BYTES);
-    rc = (int)hipMemsetAsync(scratch, 0, bytes, st);
+    rc = (int)hipMemsetAsync(scratch, 0, bytes, c.st);
     if (!rc) {
         // (public contract: aw are the attention weights; fused: softmax weights, at most 1)
-        hipLaunchKernelGGL(msda_det_absmax, dim3(2048), dim3(256), 0, st, go, n / 4, FUSED ? nullptr : aw,
-                           FUSED ? (int64_t)0 : (int64_t)B * S * M * L * TILE_P / 4, hdr);
+        hipLaunchKernelGGL(msda_det_absmax, dim3(2048), dim3(256), 0, c.st, c.go, n / 4, c.fused ? nullptr : c.aw,
+                           c.fused ? (int64_t)0 : (int64_t)c.B * c.S * c.M * c.L * TILE_P / 4, hdr);
         rc = (int)hipGetLastError();
     }
-    if (!rc)
-        rc = launch_onepass<FUSED, OnePassCfg<4, 16, 6, 1>, true>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc,
-                                                                  grad_aw, ref, ref_bstride, raw_q, out_fwd, 0, acc, hdr);
+    if (!rc) rc = launch_onepass<OnePassCfg<4, 16, 6, 1>, true>(c, 0, acc, hdr);
     if (!rc) {
-        hipLaunchKernelGGL(msda_det_finish, dim3(4096), dim3(256), 0, st, acc, hdr, grad_value, n);
+        hipLaunchKernelGGL(msda_det_finish, dim3(4096), dim3(256), 0, c.st, acc, hdr, c.grad_value, n);
         rc = (int)hipGetLastError();
     }
     return rc;
-}
-
-int msda_backward_onepass_det(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                              const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                              float *grad_loc, float *grad_aw)
-{
-    return onepass_det<0>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw, nullptr, 0, 0, nullptr);
-}
-
-int msda_backward_onepass_fused_det(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                    const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                    const float *stats, const float *out_fwd, int B, int S, int M, int D, int L,
-                                    float *grad_value, float *grad_raw)
-{
-    return onepass_det<1>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_value, grad_raw, nullptr, ref, ref_bstride, raw_q,
-                          out_fwd);
 }
 
 // job order of the grad_value-only launches: ranges (default: levels of a (tile, head) one after the other in a workgroup, guessed
@@ -1114,21 +1053,14 @@ static int onepass_order(int deflt)
 }
 
 // the grad_value half alone (DOTS = 0): the same jobs without the value window and the dot products
-// (grad_loc / grad_aw: written only when the level shapes turn out unequal on the device -- the lane-group fallback)
-int msda_backward_scatter(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                          float *grad_loc, float *grad_aw, bool standdown)
+// (grad_loc / grad_aw: written only when the level shapes turn out unequal on the device -- the lane-group fallback of the
+// public contract; the fused one passes none, and no forward output)
+int msda_backward_scatter(const MsdaBwdCall &c, int opts)
 {
-    return launch_onepass<0, OnePassCfg<4, 16, 6, 0, MVDETR_SCATTER_WGS>>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw,
-                                                         nullptr, 0, 0, nullptr, (standdown ? 1 : 0) | onepass_order(0));
-}
-
-int msda_backward_scatter_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                const float *stats, int B, int S, int M, int D, int L, float *grad_value)
-{
-    return launch_onepass<1, OnePassCfg<4, 16, 6, 0, MVDETR_SCATTER_WGS>>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_value, nullptr, nullptr,
-                                                         ref, ref_bstride, raw_q, nullptr, onepass_order(0));
+    MsdaBwdCall g = c;
+    if (c.fused) g.grad_loc = g.grad_aw = nullptr;
+    g.out_fwd = nullptr;
+    return launch_onepass<OnePassCfg<4, 16, 6, 0, MVDETR_SCATTER_WGS>>(g, opts | onepass_order(0));
 }
 
 }  // namespace mvdetr

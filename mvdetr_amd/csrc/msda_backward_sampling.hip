@@ -12,9 +12,9 @@
 // results stored level by level) measured 590 us against 190 us for the forward of the same structure --
 // 16/32-byte pieces 112/224 bytes apart are partial-line writes, which ECC memory turns into read-modify-writes.  Taps outside the
 // window read global memory.  Levels of unequal shape are detected on the device: msda_bwd_value_win
-// (msda_backward_tile.hip, always launched first) then computes all three gradients and this kernel returns.
+// (since round 5: the grad_value kernel of the route, always launched first) then computes all three gradients and this kernel returns.
 //
-// Replaces (with msda_backward.hip / msda_backward_tile.hip) the grad_sampling_loc / grad_attn_weight half of
+// Replaces (with msda_backward.hip and the grad_value kernels) the grad_sampling_loc / grad_attn_weight half of
 // ms_deformable_col2im_cuda (multiview_detector/models/ops/src/cuda/ms_deform_im2col_cuda.cuh:87-234,301-920).
 #include "common.h"
 #include "msda_dispatch.h"
@@ -92,7 +92,7 @@ __device__ __forceinline__ void corners_from_memory(const float *__restrict__ vl
 // 16/32-byte pieces per level) and its gradients one contiguous run on the way out.  One workgroup per CU (143 KB of
 // LDS at L = 7), 4 waves with up to 512 VGPRs each: the level loop is fully unrolled.
 constexpr int RS_TH = 4, RS_TW = 8, RS_R = 6, RS_WH = RS_TH + 2 * RS_R, RS_WW = RS_TW + 2 * RS_R, RS_NTOK = RS_WH * RS_WW;
-constexpr int RS_D = 16, RS_MAXL = 7, RS_THREADS = 512;
+constexpr int RS_THREADS = 512;      // (RS_D, RS_MAXL: msda_limits.h)
 static_assert(RS_NTOK % 16 == 0, "a DMA instruction covers 16 window positions");
 
 __global__ __launch_bounds__(RS_THREADS, 2) void msda_bwd_sampling_resident(
@@ -636,69 +636,37 @@ __global__ __launch_bounds__(RS_THREADS, WPE) void msda_bwd_sampling_groups(
 }
 
 template <int D, int LG, int WPE = 2, int FUSED = 0>
-static int launch_sampling_groups(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                  const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int L,
-                                  float *grad_loc, float *grad_aw, const int *local_hits, const float *ref = nullptr,
-                                  int64_t ref_bstride = 0, int raw_q = 0, const float *out_fwd = nullptr)
+static int launch_sampling_groups(const MsdaBwdCall &c, const int *probe)
 {
     constexpr int LDS = LG * RS_NTOK * D * 4;
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_sampling_groups<D, LG, WPE, FUSED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        return (cus * (WPE / 2) + 7) / 8 * 8;                 // WPE / 2 workgroups of 8 waves per CU
-    });
-    hipLaunchKernelGGL((msda_bwd_sampling_groups<D, LG, WPE, FUSED>), dim3((unsigned)blocks), dim3(RS_THREADS), LDS, st, go, value, shapes,
-                       lsi, loc, aw, B, S, M, L, grad_loc, grad_aw, local_hits, ref, ref_bstride, raw_q, out_fwd);
+    static PersistentGrid grid;
+    const int blocks = grid.fixed(&msda_bwd_sampling_groups<D, LG, WPE, FUSED>, LDS, WPE / 2);      // WPE / 2 workgroups of 8 waves per CU
+    hipLaunchKernelGGL((msda_bwd_sampling_groups<D, LG, WPE, FUSED>), dim3((unsigned)blocks), dim3(RS_THREADS), LDS, c.st, c.go, c.value,
+                       c.shapes, c.lsi, c.loc, c.aw, c.B, c.S, c.M, c.L, c.grad_loc, c.grad_aw, probe, c.ref, c.ref_bstride, c.raw_q, c.out_fwd);
     return (int)hipGetLastError();
 }
 
-static int launch_sampling_resident(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                    const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int L,
-                                    float *grad_loc, float *grad_aw, const int *local_hits)
+static int launch_sampling_resident(const MsdaBwdCall &c, const int *probe)
 {
-    const int lds = L * RS_NTOK * RS_D * 4;
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_sampling_resident),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, RS_MAXL * RS_NTOK * RS_D * 4);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        return (cus + 7) / 8 * 8;                             // one workgroup per CU (LDS)
-    });
-    hipLaunchKernelGGL(msda_bwd_sampling_resident, dim3((unsigned)blocks), dim3(RS_THREADS), lds, st, go, value, shapes, lsi,
-                       loc, aw, B, S, M, L, grad_loc, grad_aw, local_hits);
+    const int lds = c.L * RS_NTOK * RS_D * 4;
+    static PersistentGrid grid;
+    const int blocks = grid.fixed(&msda_bwd_sampling_resident, RS_MAXL * RS_NTOK * RS_D * 4, 1);     // one workgroup per CU (LDS)
+    hipLaunchKernelGGL(msda_bwd_sampling_resident, dim3((unsigned)blocks), dim3(RS_THREADS), lds, c.st, c.go, c.value, c.shapes, c.lsi,
+                       c.loc, c.aw, c.B, c.S, c.M, c.L, c.grad_loc, c.grad_aw, probe);
     return (int)hipGetLastError();
 }
 
-int msda_backward_sampling_tile(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                                float *grad_loc, float *grad_aw, const int *local_hits)
+int msda_backward_sampling(const MsdaBwdCall &c, MsdaBwdSampling which, const int *probe)
 {
-#define SAMPLING_ARGS st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_loc, grad_aw, local_hits
-    if (D == RS_D && L <= RS_MAXL && (int64_t)S * M * D * 4 < 0x7fffffffLL) return launch_sampling_resident(SAMPLING_ARGS);
-    // more levels or 32-channel heads: the same job with the levels passing through LDS in groups
-    if (D == 32) return launch_sampling_groups<32, 3>(SAMPLING_ARGS);
-    if (D == 16) return launch_sampling_groups<16, 7>(SAMPLING_ARGS);
+    if (which == MsdaBwdSampling::resident && !c.fused) return launch_sampling_resident(c, probe);
+    if (which != MsdaBwdSampling::groups) return (int)hipErrorInvalidValue;
+    // more levels or 32-channel heads: the same job with the levels passing through LDS in groups; on the raw tensor for the
+    // fused training backward's calls msda_backward_fused_sampling (6 / 7 levels of 16-channel heads) does not take
+    if (!c.fused && c.D == 32) return launch_sampling_groups<32, 3>(c, probe);
+    if (!c.fused && c.D == 16) return launch_sampling_groups<16, 7>(c, probe);
+    if (c.D == 32) return launch_sampling_groups<32, 3, 2, 1>(c, probe);
+    if (c.D == 16) return launch_sampling_groups<16, 7, 2, 1>(c, probe);
     return (int)hipErrorInvalidValue;
-}
-
-// the fused TRAINING backward's sampling half for calls msda_backward_fused_sampling (6 / 7 levels of 16-channel heads) does not
-// take: the level-groups kernel on the raw tensor (see its header)
-int msda_backward_fused_sampling_groups(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                        const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                        const float *stats, const float *out_fwd, int B, int S, int M, int D, int L, float *grad_raw)
-{
-    if ((int64_t)S * M * D * 4 >= 0x7fffffffLL) return (int)hipErrorNotSupported;
-    if (D == 32) return launch_sampling_groups<32, 3, 2, 1>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_raw, nullptr, nullptr, ref, ref_bstride, raw_q, out_fwd);
-    if (D == 16) return launch_sampling_groups<16, 7, 2, 1>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_raw, nullptr, nullptr, ref, ref_bstride, raw_q, out_fwd);
-    return (int)hipErrorNotSupported;
 }
 
 }  // namespace mvdetr

@@ -1,6 +1,6 @@
 // Multi-scale deformable attention backward, grad_value for deformable-ENCODER calls, second generation -- gfx950 (MI355X).
 //
-// msda_bwd_value_win (msda_backward_tile.hip) keeps a source level's window of grad_value in LDS as fixed-point accumulators
+// msda_bwd_value_win (rounds 1-3, docs/notes/backward_kernels_rounds_1_to_5.md) kept a source level's window of grad_value in LDS as fixed-point accumulators
 // and adds every tap corner with ds_add_u64 -- lanes = cells, one channel plane per instruction.  With learned-like offsets
 // (bias ray + ~1 px of noise) the 64 lanes of such an instruction fall on the 32 qword banks at random: 6.8 - 7.1 ns per wave
 // instruction per CU against 2.7 ns for conflict-free addresses (tools/experiments/lds_atomic_rate2.hip), and the kernel is
@@ -539,46 +539,25 @@ __global__ __launch_bounds__(256, MVDETR_VT_WGS) void msda_bwd_value_tok(
 }
 
 template <int D, int FUSED>
-int launch_value_tok(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                     const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int L,
-                     float *grad_value, float *grad_loc, float *grad_aw, const int *local_hits, const float *ref,
-                     int64_t ref_bstride, int raw_q)
+static int launch_value_tok(const MsdaBwdCall &c, const int *probe)
 {
     constexpr int LDS = 16 * 44 * 64 + 4 * 2 * 4 * 34 * 8;
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_value_tok<D, FUSED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msda_bwd_value_tok<D, FUSED>, 256, LDS) != hipSuccess || per_cu < 1)
-            per_cu = 3;
-        if (per_cu > MVDETR_VT_WGS) per_cu = MVDETR_VT_WGS;
-        return (cus * per_cu + 7) / 8 * 8;
-    });
-    hipLaunchKernelGGL((msda_bwd_value_tok<D, FUSED>), dim3((unsigned)blocks), dim3(256), LDS, st, go, value, shapes, lsi, loc, aw,
-                       B, S, M, L, grad_value, grad_loc, grad_aw, local_hits, ref, ref_bstride, raw_q);
+    static PersistentGrid grid;
+    const int blocks = grid.occupancy(&msda_bwd_value_tok<D, FUSED>, 256, LDS, 3, MVDETR_VT_WGS);
+    // (the fused contract has no gradient slots here: grad_raw comes from the sampling kernel alone)
+    hipLaunchKernelGGL((msda_bwd_value_tok<D, FUSED>), dim3((unsigned)blocks), dim3(256), LDS, c.st, c.go, c.value, c.shapes, c.lsi, c.loc, c.aw,
+                       c.B, c.S, c.M, c.L, c.grad_value, FUSED ? nullptr : c.grad_loc, FUSED ? nullptr : c.grad_aw, probe, c.ref,
+                       c.ref_bstride, c.raw_q);
     return (int)hipGetLastError();
 }
 
-int msda_backward_value_tok(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                            const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                            float *grad_value, float *grad_loc, float *grad_aw, const int *local_hits)
+int msda_backward_value_tok(const MsdaBwdCall &c, const int *probe)
 {
-    if (D == 16) return launch_value_tok<16, 0>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw, local_hits, nullptr, 0, 0);
-    if (D == 32) return launch_value_tok<32, 0>(st, go, value, shapes, lsi, loc, aw, B, S, M, L, grad_value, grad_loc, grad_aw, local_hits, nullptr, 0, 0);
+    if (!c.fused && c.D == 16) return launch_value_tok<16, 0>(c, probe);
+    if (!c.fused && c.D == 32) return launch_value_tok<32, 0>(c, probe);
+    if (c.D == 16) return launch_value_tok<16, 1>(c, probe);
+    if (c.D == 32) return launch_value_tok<32, 1>(c, probe);
     return (int)hipErrorInvalidValue;
-}
-
-int msda_backward_value_tok_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                  const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                  const float *stats, int B, int S, int M, int D, int L, float *grad_value)
-{
-    if (D == 16) return launch_value_tok<16, 1>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_value, nullptr, nullptr, nullptr, ref, ref_bstride, raw_q);
-    if (D == 32) return launch_value_tok<32, 1>(st, go, value, shapes, lsi, raw, stats, B, S, M, L, grad_value, nullptr, nullptr, nullptr, ref, ref_bstride, raw_q);
-    return (int)hipErrorNotSupported;
 }
 
 }  // namespace mvdetr

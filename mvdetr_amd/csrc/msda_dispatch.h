@@ -1,7 +1,8 @@
-// Internal dispatch between the forward kernel variants (not part of the C ABI).
+// Internal dispatch between the MSDA kernel variants, forward and backward (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "msda_backward_route.h"
 
 namespace mvdetr {
 
@@ -41,68 +42,51 @@ inline int msda_forward_tile(hipStream_t, const double *, const int64_t *, const
 // mvdetr_msda_set_forward_impl().
 int msda_fwd_impl_knob();
 
-// queries = tokens of levels [ql0, ql1) (0, L: all, the plain encoder call, which needs Lq == S)
-bool msda_tile_supported(int B, int S, int M, int D, int L, int Lq, int P, bool aligned16, int ql0, int ql1);
-
 // fused variant: reference points + raw offsets + raw logits (see msda_forward_tile.hip)
 int msda_forward_tile_fused(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
                             const float *ref, int64_t ref_bstride, const float *offsets, const float *logits,
                             int layout, int qstride_l, int qstride_w, int ql0, int ql1, int Lq, int B, int S,
                             int M, int D, int L, float *out, float *stats = nullptr);
 
-// grad_value of encoder-shaped fp32 calls through fixed-point LDS windows (msda_backward_tile.hip)
-int msda_backward_value_tile(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                             const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                             float *grad_value, float *grad_loc, float *grad_aw, const int *local_hits);
-bool msda_backward_value_tile_fits(int S, int M, int D, int L);
-// the same through token-major windows (msda_backward_value_tok.hip): what msda_backward_value_tile[_fused] dispatch to
-int msda_backward_value_tok(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                            const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                            float *grad_value, float *grad_loc, float *grad_aw, const int *local_hits);
-int msda_backward_value_tok_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                  const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                  const float *stats, int B, int S, int M, int D, int L, float *grad_value);
-// the two halves of the fused training backward (msda_backward_tile.hip, msda_backward_fused.hip)
-int msda_backward_value_tile_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                   const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                   const float *stats, int B, int S, int M, int D, int L, float *grad_value);
-int msda_backward_fused_sampling(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                 const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                 const float *stats, const float *out_fwd, int B, int S, int M, int D, int L, float *grad_raw);
-// the sampling half of the fused training backward for every other encoder shape (32-channel heads, other level counts): the
-// level-groups kernel of msda_backward_sampling.hip on the raw tensor
-int msda_backward_fused_sampling_groups(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                        const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                        const float *stats, const float *out_fwd, int B, int S, int M, int D, int L, float *grad_raw);
-// the whole encoder-shaped fp32 backward in ONE kernel (msda_backward_onepass.hip): 16-channel heads; no probe, no scratch
-bool msda_backward_onepass_supported(int B, int S, int M, int D, int L, int64_t q_floats);
-int msda_backward_onepass(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                          float *grad_loc, float *grad_aw, bool standdown);
-int msda_backward_onepass_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                const float *stats, const float *out_fwd, int B, int S, int M, int D, int L,
-                                float *grad_value, float *grad_raw);
-// the same kernel with grad_value summed in 64-bit fixed point (one binary point per call): bit-reproducible run to run.  Opt-in
+// One backward call as every launcher below receives it (host only, never a kernel parameter).  The public and the fused
+// contract share the kernels' argument slots: loc / aw hold sampling locations and attention weights, or (fused) the raw
+// offsets+logits tensor and the forward's softmax statistics; grad_loc / grad_aw their gradients, or grad_raw and null.
+// ref, ref_bstride, raw_q, out_fwd: null / 0 for the public contract.
+struct MsdaBwdCall {
+    hipStream_t st;
+    const float *go, *value;
+    const int64_t *shapes, *lsi;
+    const float *loc, *aw;
+    const float *ref;
+    int64_t ref_bstride;
+    int raw_q;
+    const float *out_fwd;
+    bool fused;
+    int B, S, M, D, L;
+    float *grad_value, *grad_loc, *grad_aw;
+};
+
+// The launchers of msda_backward_route.h's routes; which of them a call takes is decided there, they only pick the instantiation.
+// grad_value through token-major fixed-point LDS windows (msda_backward_value_tok.hip).  probe: msda_launch_locality_probe's
+// scratch (public contract), or null
+int msda_backward_value_tok(const MsdaBwdCall &c, const int *probe);
+// grad_sampling_loc / grad_attn_weight (fused: grad_raw) from LDS-staged value windows (msda_backward_sampling.hip): the resident
+// or the level-groups kernel.  probe null: the kernel takes its own sample and skips the tiles the grad_value kernel took along
+int msda_backward_sampling(const MsdaBwdCall &c, MsdaBwdSampling which, const int *probe);
+// the same for 6 / 7 levels of 16-channel heads on the raw tensor (msda_backward_fused.hip)
+int msda_backward_fused_sampling(const MsdaBwdCall &c);
+// the whole encoder-shaped fp32 backward in ONE kernel (msda_backward_onepass.hip): 16-channel heads; no probe, no scratch.
+// opts: bit 0 = stand-down (a far job computes its taps in the lane-group formulation)
+int msda_backward_onepass(const MsdaBwdCall &c, int opts);
+// the grad_value half of the same kernel alone (no value window, no dot products): units of L level jobs, guessed fixed-point
+// scale, in-kernel window shift and stand-down; job order from MVDETR_MSDA_BWD_ORDER
+int msda_backward_scatter(const MsdaBwdCall &c, int opts);
+// the one-pass kernel with grad_value summed in 64-bit fixed point (one binary point per call): bit-reproducible run to run.  Opt-in
 // (mvdetr_msda_set_backward_deterministic / MVDETR_MSDA_BWD_DETERMINISTIC=1); scratch of 8 bytes per value element, cached per (device, stream)
-bool msda_backward_deterministic_supported(int B, int S, int M, int D, int L, int64_t q_floats);
-int msda_backward_onepass_det(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                              const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                              float *grad_loc, float *grad_aw);
+int msda_backward_deterministic(const MsdaBwdCall &c);
 int msda_release_det_scratch();
-int msda_backward_onepass_fused_det(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                    const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                    const float *stats, const float *out_fwd, int B, int S, int M, int D, int L,
-                                    float *grad_value, float *grad_raw);
-// the grad_value half of the same kernel alone (no value window, no dot products): what the two-kernel backward launches for
-// grad_value since round 5 (units of L level jobs, guessed fixed-point scale, in-kernel window shift and stand-down)
-int msda_backward_scatter(hipStream_t st, const float *go, const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *aw, int B, int S, int M, int D, int L, float *grad_value,
-                          float *grad_loc, float *grad_aw, bool standdown);
-int msda_backward_scatter_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                const float *stats, int B, int S, int M, int D, int L, float *grad_value);
-// device-side locality probe shared by the kernels of a call (stream-ordered scratch of MSDA_PROBE_INTS ints):
+
+// device-side locality probe (msda_locality_probe.hip) shared by the kernels of a call (stream-ordered scratch of MSDA_PROBE_INTS ints):
 //   probe[0]              how many of MSDA_PROBE_SAMPLES sampled taps lie within MSDA_PROBE_RADIUS pixels of their own query cell
 //   probe[1 + 3 m + 0..2] for head m (< MSDA_PROBE_MAXHEADS): sum of the sampled taps' x / y displacement from their own cell in
 //                         1/16 px, and how many were summed (those within 16 px) -- where that head's taps lie.  MSDeformAttn's
@@ -174,11 +158,6 @@ __device__ __forceinline__ void msda_job_sample(const float4 &la, const float4 &
     far = tl * (float)MSDA_PROBE_NEAR_DIV < tc;
 }
 int msda_launch_locality_probe(hipStream_t st, const float *loc, const int64_t *shapes, int B, int S, int M, int L, int *hits);
-
-// grad_sampling_loc / grad_attn_weight of the same calls from LDS-staged value windows (msda_backward_sampling.hip)
-int msda_backward_sampling_tile(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                                float *grad_loc, float *grad_aw, const int *local_hits);
 
 template <typename T>
 inline MsdaFwdImpl msda_fwd_choose_impl(const T *value, const T *loc, const T *aw, const T *out, int B,

@@ -63,13 +63,15 @@ static int launch_gather(hipStream_t st, const T *value, const int64_t *shapes, 
     // Two workgroups per CU walking the items in order: the lanes in flight at any moment then belong to one compact
     // band of queries, whose taps share L2 lines.  Measured at Wildtrack size (realistic / uniform locations):
     // one item per lane 1,112 / 1,542 us; 1024 workgroups 837 / 1,437; 512 -> 537 / 950; 256 -> 819 / 1,017.
-    static const int64_t resident = [] {
+    // (not PersistentGrid: no dynamic LDS, no rounding to 8 -- a cap on the grid of a launch that may be smaller)
+    static PerDevice<int64_t> resident_of;
+    const int64_t resident = resident_of.get([] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             cus = 256;
         return (int64_t)2 * cus;
-    }();
+    });
     if (blocks > resident) blocks = resident;
     hipLaunchKernelGGL((msda_fwd_gather<T, VEC>), dim3((unsigned)blocks), dim3(block), 0, st, value,
                        shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out);
@@ -261,15 +263,10 @@ int mvdetr_msda_forward_fused_levels_f32(void *stream, const float *value, const
 int mvdetr_msda_fused_train_supported(int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
                                       int num_point)
 {
-    using namespace mvdetr;
-    // every deformable-encoder shape the LDS-tiled kernels take: up to 16 levels (of equal shape: the caller's promise), 16- or
-    // 32-channel heads, 4 points, queries = tokens.  6 / 7 levels of 16-channel heads (MVDeTr's own) run msda_fwd_group2 +
-    // msda_bwd_onepass<grad_value only> + msda_bwd_fused_sampling; other level counts the one-pass backward (16 channels) or
-    // msda_bwd_value_tok + the level-groups sampling kernel (32 channels) behind the inference forward + a statistics pass.
-    if (!msda_tile_supported(batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, true, 0, num_levels)) return 0;
-    // (the whole raw tensor, all batch elements, in 32-bit float offsets: msda_group_fits; one element's in 2^29 for the backward)
-    if ((int64_t)spatial_size * num_heads * num_levels * num_point * 3 >= ((int64_t)1 << 29)) return 0;
-    return (int64_t)batch * spatial_size * num_heads * num_levels * num_point * 3 < ((int64_t)1 << 30) ? 1 : 0;
+    // 6 / 7 levels of 16-channel heads (MVDeTr's own) run msda_fwd_group2 + msda_bwd_onepass<grad_value only> +
+    // msda_bwd_fused_sampling; other level counts the one-pass backward (16 channels) or msda_bwd_value_tok + the level-groups
+    // sampling kernel (32 channels) behind the inference forward + a statistics pass (msda_backward_route.h).
+    return mvdetr::msda_fused_train_supported(batch, spatial_size, num_heads, channels, num_levels, num_query, num_point) ? 1 : 0;
 }
 
 int mvdetr_msda_forward_fused_train_f32(void *stream, const float *value, const int64_t *spatial_shapes,

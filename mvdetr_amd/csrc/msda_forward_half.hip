@@ -108,7 +108,7 @@ static int launch_half(hipStream_t st, const uint16_t *value, const int64_t *sha
     const int block = 256;
     int64_t blocks = (total + block - 1) / block;
     // as msda_forward.hip's gather launch: two workgroups per CU walking the items in order keep the lanes in flight in
-    // one compact band of queries
+    // one compact band of queries (not PersistentGrid: a cap of 2 workgroups per CU, no dynamic LDS, no rounding to 8, not cached)
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)

@@ -82,37 +82,13 @@ int msda_softmax_stats(hipStream_t st, const float *logits, SamplingLayout lay, 
     return (int)hipGetLastError();
 }
 
-bool msda_tile_supported(int B, int S, int M, int D, int L, int Lq, int P, bool aligned16, int ql0, int ql1)
-{
-    if (!aligned16 || P != TILE_P || L > TILE_MAX_LEVELS || B < 1) return false;
-    // the LDS-DMA window copies (msda_forward_group.hip, msda_backward_sampling.hip) address one batch element's value
-    // tokens through a 32-bit buffer descriptor whose out-of-range sentinel is offset 2^31: a per-batch value tensor of
-    // 2 GiB or more would alias it.  Such calls take the gather / lane-group kernels (64-bit addressing).
-    if ((int64_t)S * M * D * 4 >= 0x7fffffffLL) return false;
-    const bool all_levels = ql0 == 0 && ql1 == L;
-    if (ql0 < 0 || ql1 <= ql0 || ql1 > L || (all_levels ? Lq != S : Lq > S)) return false;
-    return (D == 16 && M % 2 == 0) || D == 32;
-}
-
 template <typename Cfg, int FUSED>
 static int launch_tile(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
                        const float *loc, const float *aw, const float *ref, int64_t ref_bstride, SamplingLayout lay,
                        QueryLevels qr, int B, int S, int M, int L, float *out, const int *local_hits)
 {
-    static PerDevice<int> blocks_of;
-    const int blocks = blocks_of.get([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tile<Cfg, FUSED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msda_fwd_tile<Cfg, FUSED>, Cfg::THREADS,
-                                                         Cfg::LDS_BYTES) != hipSuccess || per_cu < 1)
-            per_cu = 2;
-        int n = cus * per_cu;
-        return (n + 7) / 8 * 8;                          // keep the XCD interleave whole
-    });
+    static PersistentGrid grid;
+    const int blocks = grid.occupancy(&msda_fwd_tile<Cfg, FUSED>, Cfg::THREADS, Cfg::LDS_BYTES, 2);
     static const KernelResources res = kernel_resources(reinterpret_cast<const void *>(&msda_fwd_tile<Cfg, FUSED>));
     msda_note_forward_kernel("msda_fwd_tile", &res);
     hipLaunchKernelGGL((msda_fwd_tile<Cfg, FUSED>), dim3((unsigned)blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES,

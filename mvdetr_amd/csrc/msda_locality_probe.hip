@@ -1,24 +1,9 @@
-// Multi-scale deformable attention backward for deformable-ENCODER calls: the locality probe of rounds 2-4's two-kernel
-// path and the entry points of its grad_value half -- gfx950 (MI355X).
-//
-// History of the grad_value kernels (the generic backward, msda_backward.hip, sends every bilinear corner of every tap to
-// memory as fp32 atomics: 3.15 ms at Wildtrack size; LDS fp32 atomics are no way out -- ds_add_f32: 80 ns per wave
-// instruction per CU -- but LDS INTEGER atomics run at 1.8 / 2.7 ns for 32 / 64 bits):
-//   round 1-3  msda_bwd_value_win: channel-major fixed-point windows, lanes = cells (526 -> 390 us; removed in round 5)
-//   round 4    msda_bwd_value_tok (msda_backward_value_tok.hip): token-major windows, lanes = (cell, corner, channel pair);
-//              still what 32-channel heads and MVDETR_MSDA_BWD_IMPL=twopass run
-//   round 5    msda_bwd_onepass<DOTS = 0> (msda_backward_onepass.hip): the same accumulation, jobs sequenced level by level
-//              with a guessed fixed-point scale, no probe launch -- the default for 16-channel heads
-// grad_sampling_loc / grad_attn_weight come from msda_backward_sampling.hip / msda_backward_fused.hip.
-//
-// Replaces (with the files above) ms_deformable_col2im_cuda's grad_value accumulation
-// (multiview_detector/models/ops/src/cuda/ms_deform_im2col_cuda.cuh:87-152,301-920).
+// Multi-scale deformable attention for deformable-ENCODER calls: the locality probe the forward tile kernels and the two-kernel
+// backward launch in front of themselves -- gfx950 (MI355X).  What it writes and who reads it: msda_dispatch.h.
+// (The grad_value kernels that lived here: docs/notes/backward_kernels_rounds_1_to_5.md.)
 #include "common.h"
 #include "msda_dispatch.h"
 #include "msda_tile.h"
-#include "msda_backward_lanes.h"
-#include <stdlib.h>
-#include <string.h>
 
 namespace mvdetr {
 
@@ -68,31 +53,6 @@ int msda_launch_locality_probe(hipStream_t st, const float *loc, const int64_t *
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(msda_locality_probe, dim3(MSDA_PROBE_SAMPLES / 256), dim3(256), 0, st, loc, shapes, B, S, M, L, probe);
     return (int)hipGetLastError();
-}
-
-int msda_backward_value_tile(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                             const int64_t *lsi, const float *loc, const float *aw, int B, int S, int M, int D, int L,
-                             float *grad_value, float *grad_loc, float *grad_aw, const int *local_hits)
-{
-    return msda_backward_value_tok(st, go, value, shapes, lsi, loc, aw, B, S, M, D, L, grad_value, grad_loc, grad_aw, local_hits);
-}
-
-// msda_bwd_value_tok addresses one batch element's tensors with 32-bit byte offsets: larger calls keep the generic kernel
-bool msda_backward_value_tile_fits(int S, int M, int D, int L)
-{
-    const int64_t lim = (int64_t)1 << 32;
-    return (D == 16 || D == 32) && (int64_t)S * M * L * TILE_P * 2 * 4 < lim && (int64_t)S * M * D * 4 < lim;
-}
-
-// grad_value of the fused training backward: raw offsets / logits + the forward's statistics (see the kernel's header)
-int msda_backward_value_tile_fused(hipStream_t st, const float *go, const float *value, const int64_t *shapes,
-                                   const int64_t *lsi, const float *raw, int raw_q, const float *ref, int64_t ref_bstride,
-                                   const float *stats, int B, int S, int M, int D, int L, float *grad_value)
-{
-    const int64_t lim = (int64_t)1 << 32;
-    if ((int64_t)S * raw_q * 4 < lim && (int64_t)S * M * D * 4 < lim)
-        return msda_backward_value_tok_fused(st, go, value, shapes, lsi, raw, raw_q, ref, ref_bstride, stats, B, S, M, D, L, grad_value);
-    return (int)hipErrorNotSupported;
 }
 
 }  // namespace mvdetr

@@ -1,12 +1,10 @@
 // Shared configuration of the LDS-tiled MSDA kernels (forward: msda_forward_tile.hip, backward:
-// msda_backward_tile.hip).  Internal, not part of the C ABI.
+// msda_backward_*.hip).  Internal, not part of the C ABI.
 #pragma once
 #include "common.h"
+#include "msda_limits.h"
 
 namespace mvdetr {
-
-constexpr int TILE_MAX_LEVELS = 16;     // 64-bit miss mask = L * P bits with P == 4
-constexpr int TILE_P = 4;
 
 // R_: halo in x (and in y unless RY_ is given).  The LDS-DMA window copies start every window row at a wave-uniform LDS
 // base; rows of WW * SLICE * 4 bytes that are not multiples of 512 bytes (WW = 26 at R = 5) fault on gfx950, so a narrower

@@ -297,6 +297,12 @@ def last_forward_kernel() -> str:
     return _lib.lib().mvdetr_msda_last_forward_kernel().decode()
 
 
+def last_backward_route() -> str:
+    """Name of the route the last backward on this thread took ('twopass', 'fused-split', ...; 'none' before the first;
+    bench/tests only).  Autograd runs backwards on a thread of its own: ask on the thread that made the C call."""
+    return _lib.lib().mvdetr_msda_last_backward_route().decode()
+
+
 def last_forward_resources():
     """What the code object records for the kernel instantiation the last forward on this thread launched:
     ``{"num_regs", "scratch_bytes_per_lane", "static_lds_bytes"}`` (hipFuncGetAttributes; scratch > 0 = it spills), or
@@ -332,7 +338,7 @@ def backward_deterministic() -> bool:
 
 
 def backward_deterministic_supported(B: int, S: int, M: int, D: int, L: int, Lq: int, P: int) -> bool:
-    """The calls the deterministic mode serves (csrc/msda_backward_onepass.hip: msda_backward_deterministic_supported): fp32
+    """The calls the deterministic mode serves (csrc/msda_backward_route.h: msda_backward_deterministic_supported): fp32
     deformable-encoder calls with 16-channel heads and 4 points, at most 16 levels, one batch element's tensors below 2 GiB and
     S * L * P < 2^24 (the 64-bit sums' headroom).  Everything else is refused with hipErrorNotSupported while the mode is on."""
     return (D == 16 and P == 4 and Lq == S and 1 <= L <= 16 and S * M * D * 4 < 2 ** 31 and S * M * L * P * 2 * 4 < 2 ** 31

@@ -97,6 +97,7 @@ def _child(family, out_path):
         for case in BWD_CASES:
             value, shapes, lsi, loc, aw, go = [x.cuda() for x in _bwd_case(case)]
             res = [x.cpu() for x in MSDA.ms_deform_attn_backward(value, shapes, lsi, loc, aw, go, 64)]
+            route = MSDA.last_backward_route()
             if case == "bwd_wildtrack":
                 out = MSDA.ms_deform_attn_forward(value, shapes, lsi, loc, aw, 64)
                 lhs = (go.double() * out.double()).sum().item()
@@ -106,6 +107,7 @@ def _child(family, out_path):
                 res = [torch.tensor([lhs, rhs_v, rhs_a], dtype=torch.float64), res[1][:, sub].contiguous(), res[2][:, sub].contiguous(),
                        res[0].double().abs().sum()]
             results[case] = res
+            results["route:" + case] = route
         from helpers import skew_case
         for case in SKEW_KNOB_CASES:
             form, x = skew_case(case)
@@ -116,6 +118,7 @@ def _child(family, out_path):
                 value, shapes, lsi, ref, raw, _, go = [t.cuda() for t in x]
                 out, stats = MSDA.ms_deform_attn_forward_fused_train(value, shapes, lsi, ref, raw)
                 results["skew:" + case] = [t.cpu() for t in MSDA.ms_deform_attn_backward_fused(go, value, shapes, lsi, ref, raw, stats, out)]
+            results["route:skew:" + case] = MSDA.last_backward_route()
     elif family == "fwd":
         for case in FWD_CASES:
             value, shapes, lsi, loc, aw = [x.cuda() for x in _fwd_case(case)]
@@ -153,6 +156,25 @@ def _run_child(family, env):
 pytestmark = pytest.mark.gpu
 
 
+def _expected_bwd_route(case, env):
+    """The route name mvdetr_msda_last_backward_route() must report (csrc/msda_backward_route.h; INTEGRATION.md, knob table):
+    the public entry runs the knob's route, `twopass` by default, and 32-channel heads `twopass` under every setting but
+    `atomic`; the fused entry `fused-split` unless the knob says `twopass` or `onepass`."""
+    impl = env.get("MVDETR_MSDA_BWD_IMPL", "unset")
+    if case.startswith("fused_"):
+        return {"twopass": "fused-twopass", "onepass": "fused-onepass"}.get(impl, "fused-split")
+    if impl == "atomic":
+        return "atomic"
+    if impl == "unset" or case == "bwd_encoder_d32":
+        return "twopass"
+    return impl
+
+
+def _assert_bwd_route(case, env):
+    got = _run_child("bwd", env)["route:" + ("skew:" + case if case in SKEW_KNOB_CASES else case)]
+    assert got == _expected_bwd_route(case, env), (case, env, got)
+
+
 @pytest.mark.parametrize("env", BWD_ROUTES, ids=_route_id)
 @pytest.mark.parametrize("case", BWD_CASES[:-1])
 def test_backward_routes_vs_oracle(case, env):
@@ -162,6 +184,7 @@ def test_backward_routes_vs_oracle(case, env):
     value, shapes, lsi, loc, aw, go = _bwd_case(case)
     ref = c_oracle.msda_backward(value.double(), shapes, lsi, loc.double(), aw.double(), go.double())
     got = _run_child("bwd", env)[case]
+    _assert_bwd_route(case, env)
     W = float(shapes[0, 1])
     # (grad_loc of a tap within fp32 rounding of a texel centre depends on which side the rounding falls: the blend's slope
     # jumps there -- such taps are excluded, as in test_msda_gpu.py)
@@ -185,6 +208,7 @@ def test_backward_routes_at_wildtrack_size(env):
     from oracle import c_oracle
     value, shapes, lsi, loc, aw, go = _bwd_case("bwd_wildtrack")
     sums, gl, ga, gv_abs = _run_child("bwd", env)["bwd_wildtrack"]
+    _assert_bwd_route("bwd_wildtrack", env)
     lhs, rhs_v, rhs_a = sums.tolist()
     assert abs(lhs - rhs_v) < 1e-6 * (abs(lhs) + 1e3) and abs(lhs - rhs_a) < 1e-6 * (abs(lhs) + 1e3)
     assert gv_abs.item() > 1e3
@@ -203,6 +227,7 @@ def test_backward_routes_per_block_under_mass_skew(case, env):
     within 2e-5 of its [b, level, head] block's maximum, the sampling gradients within 2e-4 of theirs)."""
     sys.path.insert(0, HERE)
     from helpers import assert_skew_bars
+    _assert_bwd_route(case, env)
     assert_skew_bars(case, _run_child("bwd", env)["skew:" + case])
 
 
