@@ -99,6 +99,31 @@ int mvdetr_msda_forward_fused_f32(void *stream, const float *value, const int64_
                                   int logits_query_stride, int batch, int spatial_size, int num_heads,
                                   int channels, int num_levels, int num_query, int num_point, float *out);
 
+/* 16-bit storage variant of the fused forward (inference; an addition, the ABI version above is unchanged), for the ONE form
+ * MSDeformAttn calls it in (csrc/msda_forward_fused_half.hip):
+ *   value  [batch, spatial_size, num_heads, channels]  16-bit words (IEEE binary16 `_f16` / bfloat16 `_bf16`)
+ *   raw    [batch, Lq, >= num_heads*num_levels*12]  16-bit, the slice-interleaved tensor with the level outermost (bits 4|16
+ *          above; g = 32 / channels heads per run as in the fp32 layout, so the same permuted Linear produces it);
+ *          raw_query_stride elements between queries (0 = dense), a multiple of 4
+ *   reference_points  [batch or 1, num_levels, Lq, 2]  FP32, one point per (query, level), level-major (bits 2|8);
+ *          ref_batch_stride floats between batch elements (0 = shared)
+ *   out    [batch, Lq, num_heads*channels]  16-bit
+ * Softmax over the num_levels*4 logits, loc = ref + offset / (W, H) and the bilinear blend are fp32; every output element is
+ * rounded once, to nearest-even.  Served: channels 16 or 32, num_point 4, num_levels <= 16 OF EQUAL SHAPE (device data: on
+ * other shapes every output element is NaN), num_query == spatial_size, 16-byte aligned value / raw / out:
+ * mvdetr_msda_fused_half_supported() returns 1 for such dimensions, and the forward returns hipErrorNotSupported (801) for
+ * anything else.  Kernel name: "msda_fwd_fused_half". */
+int mvdetr_msda_fused_half_supported(int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                                     int num_point);
+int mvdetr_msda_forward_fused_f16(void *stream, const uint16_t *value, const int64_t *spatial_shapes,
+                                  const int64_t *level_start_index, const float *reference_points, int64_t ref_batch_stride,
+                                  const uint16_t *raw, int raw_query_stride, int batch, int spatial_size, int num_heads,
+                                  int channels, int num_levels, int num_point, uint16_t *out);
+int mvdetr_msda_forward_fused_bf16(void *stream, const uint16_t *value, const int64_t *spatial_shapes,
+                                   const int64_t *level_start_index, const float *reference_points, int64_t ref_batch_stride,
+                                   const uint16_t *raw, int raw_query_stride, int batch, int spatial_size, int num_heads,
+                                   int channels, int num_levels, int num_point, uint16_t *out);
+
 /* The same with the queries restricted to the tokens of levels [query_level_begin, query_level_end): the
  * encoder call of ONE rank of a query-sharded run (cameras = levels partitioned over GPUs; SURVEY 8e option
  * B -- not in the reference, which is single-device).  `value` still holds all spatial_size tokens;
@@ -193,6 +218,17 @@ int mvdetr_warp_perspective_forward_f64(void *stream, const double *src, const d
                                         int channels, int src_h, int src_w, int dst_h, int dst_w,
                                         int layout_nhwc, double *dst);
 
+/* 16-bit storage variants of the forward (inference; an addition, the ABI version above is unchanged): src and dst are IEEE
+ * binary16 (`_f16`) / bfloat16 (`_bf16`) words, M stays FP32; the source position is computed in fp64 exactly as above, the
+ * blend weights and the blend are fp32, and every output element is rounded once, to nearest-even.  All four layout
+ * combinations and bit 2 (nearest) are taken: channel-last on both sides with channels % 8 == 0 and 16-byte aligned tensors
+ * runs "warp_fwd_cl_half" (8 channels per lane), everything else "warp_fwd_half" (2-byte accesses).  No backward, no host
+ * entry. */
+int mvdetr_warp_perspective_forward_f16(void *stream, const uint16_t *src, const float *M, int n, int channels, int src_h,
+                                        int src_w, int dst_h, int dst_w, int layout_nhwc, uint16_t *dst);
+int mvdetr_warp_perspective_forward_bf16(void *stream, const uint16_t *src, const float *M, int n, int channels, int src_h,
+                                         int src_w, int dst_h, int dst_w, int layout_nhwc, uint16_t *dst);
+
 /* Gradient of the warp w.r.t. src (what autograd reaches through grid_sample in the reference).
  *   grad_dst [n, channels, dst_h, dst_w] (or NHWC if layout_nhwc bit 0)
  *   grad_src [n, channels, src_h, src_w] (or NHWC if layout_nhwc bit 1, same restrictions as the forward);
@@ -266,6 +302,17 @@ int mvdetr_add_layernorm_f32(void *stream, const float *x, const float *residual
 int mvdetr_add_layernorm_add_f32(void *stream, const float *x, const float *residual, const float *weight,
                                  const float *bias, const float *add2, int64_t add2_rows, int64_t rows, int cols,
                                  float eps, float *out, float *out2);
+
+/* 16-bit storage variants (inference; an addition, the ABI version above is unchanged): x, residual, weight, bias, add2, out
+ * and out2 are IEEE binary16 (`_f16`) / bfloat16 (`_bf16`) words.  The sum x + residual, its mean and variance and the
+ * normalised row are fp32; out is rounded once, and out2 is formed from the UNROUNDED row plus add2 and rounded once.  The same
+ * cols set; pointers aligned to (cols/64)*2 bytes (16-byte aligned tensors take 16-byte accesses): 801 otherwise. */
+int mvdetr_add_layernorm_add_f16(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
+                                 const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows, int cols,
+                                 float eps, uint16_t *out, uint16_t *out2);
+int mvdetr_add_layernorm_add_bf16(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
+                                  const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows, int cols,
+                                  float eps, uint16_t *out, uint16_t *out2);
 
 /* ---- The ResNet trunk's inference epilogues (csrc/trunk_epilogue.hip) ---------------------------
  * Eval-mode BatchNorm2d with what follows it in a residual block, one pass over channel-last fp32 activations:

@@ -27,6 +27,7 @@ _MSDA_FWD_HOST = [_vp] * 5 + [_i] * 7 + [_vp]
 _MSDA_BWD_HOST = [_vp] * 6 + [_i] * 7 + [_vp] * 3
 _WARP_HOST = [_vp] * 2 + [_i] * 8 + [_vp]
 _MSDA_FUSED = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 10 + [_vp]
+_MSDA_FUSED_HALF = [_vp] * 5 + [ctypes.c_int64, _vp] + [_i] * 7 + [_vp]
 _MSDA_FUSED_LEVELS = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 12 + [_vp]
 _DC_FWD = [_vp] * 5 + [_i] * 15 + [_vp]
 _DC_BWD = [_vp] * 5 + [_i] * 15 + [_vp] * 3
@@ -72,6 +73,9 @@ SIGNATURES = {
     "mvdetr_msda_forward_bf16": (_MSDA_FWD, _i),
     "mvdetr_msda_fused_supported": ([_i] * 7, _i),
     "mvdetr_msda_forward_fused_f32": (_MSDA_FUSED, _i),
+    "mvdetr_msda_fused_half_supported": ([_i] * 7, _i),
+    "mvdetr_msda_forward_fused_f16": (_MSDA_FUSED_HALF, _i),
+    "mvdetr_msda_forward_fused_bf16": (_MSDA_FUSED_HALF, _i),
     "mvdetr_msda_fused_levels_supported": ([_i] * 9, _i),
     "mvdetr_msda_forward_fused_levels_f32": (_MSDA_FUSED_LEVELS, _i),
     "mvdetr_msda_fused_train_supported": ([_i] * 7, _i),
@@ -81,12 +85,16 @@ SIGNATURES = {
     "mvdetr_msda_backward_f64": (_MSDA_BWD, _i),
     "mvdetr_add_layernorm_f32": ([_vp] * 5 + [ctypes.c_int64, _i, ctypes.c_float, _vp], _i),
     "mvdetr_add_layernorm_add_f32": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
+    "mvdetr_add_layernorm_add_f16": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
+    "mvdetr_add_layernorm_add_bf16": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
     "mvdetr_bn_act_f32": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),
     "mvdetr_bn_relu_maxpool_f32": ([_vp] * 6 + [ctypes.c_float] + [_i] * 4 + [_vp], _i),
     "mvdetr_trunk_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_trunk_launch_count": ([], ctypes.c_int64),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f64": (_WARP, _i),
+    "mvdetr_warp_perspective_forward_f16": (_WARP, _i),
+    "mvdetr_warp_perspective_forward_bf16": (_WARP, _i),
     "mvdetr_warp_perspective_backward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_backward_f64": (_WARP, _i),
     "mvdetr_warp_perspective_backward_tagged_f32": ([_vp] * 3 + [_i] * 7 + [ctypes.c_uint64, _vp], _i),

@@ -8,6 +8,7 @@
 // normalised row is written once: 116 MB of traffic instead of 232 MB.  128 channels (the encoder's width) take
 // add_layernorm_rows128x2 below: two rows per wave, 24.7 -> 18.6 us at 75,600 rows (0.78 of the HBM roofline).
 #include "common.h"
+#include "half_types.h"
 #include "../../include/mvdetr_ops.h"
 
 namespace mvdetr {
@@ -110,6 +111,109 @@ __global__ __launch_bounds__(256) void add_layernorm_rows128x2(const float *__re
     }
 }
 
+// 16-bit storage (float16 / bfloat16; inference): x, residual, gamma, beta, add2, out and out2 are 16-bit words, the sum
+// x + residual, its mean and variance and the normalised row are fp32, and each output element is rounded once -- out2 from
+// the UNROUNDED y + add2.  A lane holds VEC consecutive channels (VEC = 8: one 16-byte access, COLS / 8 lanes per row and
+// 512 / COLS rows per wave; VEC = COLS / 64: one row per wave, for tensors that are not 16-byte aligned); the sums are
+// xor-shuffles among the lanes of a row.
+template <typename C, int COLS, int VEC>
+__global__ __launch_bounds__(256) void add_layernorm_rows_half(const uint16_t *__restrict__ x, const uint16_t *__restrict__ res,
+                                                               const uint16_t *__restrict__ gamma, const uint16_t *__restrict__ beta,
+                                                               const uint16_t *__restrict__ add2, int64_t add2_rows, int64_t rows,
+                                                               float eps, uint16_t *__restrict__ out, uint16_t *__restrict__ out2)
+{
+    constexpr int LPR = COLS / VEC, RPW = 64 / LPR;          // lanes per row, rows per wave
+    static_assert(LPR >= 1 && LPR <= 64 && RPW * LPR == 64, "a wave holds whole rows");
+    const int lane = threadIdx.x & 63, sub = lane % LPR, rsel = lane / LPR;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    float g[VEC], bt[VEC];
+    if (gamma) {
+        const Raw<VEC> gr = *reinterpret_cast<const Raw<VEC> *>(gamma + sub * VEC);
+        const Raw<VEC> br = *reinterpret_cast<const Raw<VEC> *>(beta + sub * VEC);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { g[i] = C::up(gr.v[i]); bt[i] = C::up(br.v[i]); }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { g[i] = 1.f; bt[i] = 0.f; }
+    }
+    for (int64_t r0 = wave * RPW; r0 < rows; r0 += nwaves * RPW) {
+        const int64_t r = r0 + rsel;
+        const bool live = r < rows;                           // (the last wave's upper rows idle, converged for the shuffles)
+        const int64_t rr = live ? r : rows - 1;
+        const Raw<VEC> xr = *reinterpret_cast<const Raw<VEC> *>(x + rr * COLS + sub * VEC);
+        float v[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = C::up(xr.v[i]);
+        if (res) {
+            const Raw<VEC> q = *reinterpret_cast<const Raw<VEC> *>(res + rr * COLS + sub * VEC);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) v[i] += C::up(q.v[i]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) s += v[i];
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float mean = s * (1.f / COLS);
+        float m2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) m2 += (v[i] - mean) * (v[i] - mean);
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
+        const float rstd = rsqrtf(m2 * (1.f / COLS) + eps);
+        float y[VEC];
+        Raw<VEC> yo;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            y[i] = (v[i] - mean) * rstd * g[i] + bt[i];
+            yo.v[i] = C::down(y[i]);
+        }
+        if (live) *reinterpret_cast<Raw<VEC> *>(out + r * COLS + sub * VEC) = yo;
+        if (out2) {                                           // second output: the unrounded y + add2 (rows of add2 repeat)
+            const Raw<VEC> p = *reinterpret_cast<const Raw<VEC> *>(add2 + (rr % add2_rows) * COLS + sub * VEC);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) yo.v[i] = C::down(y[i] + C::up(p.v[i]));
+            if (live) *reinterpret_cast<Raw<VEC> *>(out2 + r * COLS + sub * VEC) = yo;
+        }
+    }
+}
+
+template <typename C, int COLS>
+static int add_layernorm_half_launch(hipStream_t st, bool a16, const uint16_t *x, const uint16_t *res, const uint16_t *gamma,
+                                     const uint16_t *beta, const uint16_t *add2, int64_t add2_rows, int64_t rows, float eps,
+                                     uint16_t *out, uint16_t *out2)
+{
+    const int rpw = a16 ? 512 / COLS : 1;
+    const int64_t want = (rows + 4 * rpw - 1) / (4 * rpw);                           // four waves per block
+    const unsigned blocks = (unsigned)(want < 256 * 16 ? want : 256 * 16);          // grid-stride above 16 blocks per CU
+    if (a16) hipLaunchKernelGGL((add_layernorm_rows_half<C, COLS, 8>), dim3(blocks), dim3(256), 0, st, x, res, gamma, beta, add2, add2_rows, rows, eps, out, out2);
+    else hipLaunchKernelGGL((add_layernorm_rows_half<C, COLS, COLS / 64>), dim3(blocks), dim3(256), 0, st, x, res, gamma, beta, add2, add2_rows, rows, eps, out, out2);
+    return (int)hipGetLastError();
+}
+
+template <typename C>
+static int add_layernorm_half_entry(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
+                                    const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows, int cols,
+                                    float eps, uint16_t *out, uint16_t *out2)
+{
+    if (rows < 0 || cols <= 0) return (int)hipErrorInvalidValue;
+    if (rows == 0) return 0;
+    if (!x || !out || (weight == nullptr) != (bias == nullptr)) return (int)hipErrorInvalidValue;
+    if ((add2 == nullptr) != (out2 == nullptr) || (add2 && add2_rows <= 0)) return (int)hipErrorInvalidValue;
+    if (cols != 64 && cols != 128 && cols != 256) return (int)hipErrorNotSupported;
+    auto all_aligned = [&](size_t al) {
+        return aligned(x, al) && aligned(out, al) && (!residual || aligned(residual, al)) &&
+               (!weight || (aligned(weight, al) && aligned(bias, al))) && (!add2 || (aligned(add2, al) && aligned(out2, al)));
+    };
+    if (!all_aligned((size_t)(cols / 64) * 2)) return (int)hipErrorNotSupported;      // a lane's cols / 64 elements as one access
+    const bool a16 = all_aligned(16);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (cols == 64) return add_layernorm_half_launch<C, 64>(st, a16, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
+    if (cols == 128) return add_layernorm_half_launch<C, 128>(st, a16, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
+    return add_layernorm_half_launch<C, 256>(st, a16, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
+}
+
 }  // namespace mvdetr
 
 extern "C" int mvdetr_add_layernorm_f32(void *stream, const float *x, const float *residual, const float *weight,
@@ -147,4 +251,18 @@ extern "C" int mvdetr_add_layernorm_add_f32(void *stream, const float *x, const 
     else if (cols == 128) hipLaunchKernelGGL(add_layernorm_rows<2>, dim3(blocks), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
     else hipLaunchKernelGGL(add_layernorm_rows<4>, dim3(blocks), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
     return (int)hipGetLastError();
+}
+
+extern "C" int mvdetr_add_layernorm_add_f16(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
+                                            const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows,
+                                            int cols, float eps, uint16_t *out, uint16_t *out2)
+{
+    return mvdetr::add_layernorm_half_entry<mvdetr::F16>(stream, x, residual, weight, bias, add2, add2_rows, rows, cols, eps, out, out2);
+}
+
+extern "C" int mvdetr_add_layernorm_add_bf16(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
+                                             const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows,
+                                             int cols, float eps, uint16_t *out, uint16_t *out2)
+{
+    return mvdetr::add_layernorm_half_entry<mvdetr::BF16>(stream, x, residual, weight, bias, add2, add2_rows, rows, cols, eps, out, out2);
 }

@@ -9,43 +9,13 @@
 // One lane owns VEC consecutive channels of one (b, q, head): with D = 32 and VEC = 4 the eight lanes of a head read
 // one contiguous 64-byte token segment per bilinear corner.
 #include "common.h"
+#include "half_types.h"
 #include "../../include/mvdetr_ops.h"
 
 namespace mvdetr {
 
 struct KernelResources;
 void msda_note_forward_kernel(const char *name, const KernelResources *res = nullptr);
-
-struct F16 {
-    static __device__ __forceinline__ float up(uint16_t h)
-    {
-        _Float16 x;
-        __builtin_memcpy(&x, &h, 2);
-        return (float)x;
-    }
-    static __device__ __forceinline__ uint16_t down(float f)
-    {
-        const _Float16 x = (_Float16)f;                   // v_cvt_f16_f32: round to nearest even
-        uint16_t h;
-        __builtin_memcpy(&h, &x, 2);
-        return h;
-    }
-};
-
-struct BF16 {
-    static __device__ __forceinline__ float up(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-    static __device__ __forceinline__ uint16_t down(float f)
-    {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);      // quiet NaN
-        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                      // round to nearest even
-    }
-};
-
-template <int VEC> struct Raw;                            // VEC 16-bit values as one access
-template <> struct Raw<1> { uint16_t v[1]; };
-template <> struct alignas(8) Raw<4> { uint16_t v[4]; };
-template <> struct alignas(16) Raw<8> { uint16_t v[8]; };
 
 template <typename C, int VEC>
 __global__ __launch_bounds__(256) void msda_fwd_gather_half(

@@ -16,6 +16,7 @@
 // channels split over the block's 4 waves.  For the channel-last output the 64x64 (pixel, channel) tile is
 // transposed through LDS (65-float rows, conflict-free both ways) so the stores are 256-byte rows.
 #include "common.h"
+#include "half_types.h"
 #include "../../include/mvdetr_ops.h"
 #include <atomic>
 #include <map>
@@ -110,6 +111,8 @@ __device__ __forceinline__ void load_pair(const T *p, bool v0, bool v1, T &a, T 
 
 // a destination pixel's bilinear footprint in the source view: what the channel-last kernels and (round 5) warp_fwd share
 // per tile through LDS
+// (T is the type the blend is COMPUTED in and the matrices come in: the tensor's own type for fp32 / fp64 tensors, float for
+// the 16-bit kernels, whose storage type is a converter of half_types.h and never appears here)
 template <typename T> struct WarpTexel {
     int o00;                     // element offset of corner (y0, x0) inside the view, in texels (not scaled by C)
     T w00, w01, w10, w11;
@@ -1314,6 +1317,115 @@ static int warp_entry(bool backward, void *stream, const T *a, const T *Mv, int 
     return (int)hipGetLastError();
 }
 
+// ---- 16-bit storage (float16 / bfloat16), forward only (inference) ---------------------------------------------------------
+// src and dst are 16-bit words, the matrices fp32; the source position is the same fp64 source_position / make_coord, the
+// blend weights and the blend are fp32 (WarpTexel<float>: storage type and compute type are separate here), and every
+// output element is rounded once, to nearest-even.  warp_fwd_cl_half is warp_fwd_cl with 8 channels (16 bytes) per lane:
+// channel-last on both sides, the layout a channels_last trunk hands to the shadow transformer.
+template <typename C>
+__global__ __launch_bounds__(WARP_CL_THREADS) void warp_fwd_cl_half(
+    const uint16_t *__restrict__ src, const float *__restrict__ Mv, int N, int Cn, int h, int w, int H, int W,
+    int nearest, uint16_t *__restrict__ dst)
+{
+    constexpr int VEC = 8;
+    __shared__ WarpTexel<float> tex[WARP_PIX];
+    WarpBlock wb;
+    if (!warp_block(N, H, W, 1, wb)) return;
+    const int n = wb.n;
+    if (threadIdx.x < WARP_PIX) {
+        const int i = wb.i0 + threadIdx.x / WARP_TW, j = wb.j0 + threadIdx.x % WARP_TW;
+        tex[threadIdx.x] = warp_texel(Mv + (int64_t)n * 9, i, j, h, w, i < H && j < W, nearest);
+    }
+    __syncthreads();
+    const int chunks = Cn / VEC;                                  // 16-byte chunks per pixel
+    const uint16_t *view = src + (int64_t)n * h * w * Cn;
+    const int rowC = w * Cn;
+    for (int item = threadIdx.x; item < WARP_PIX * chunks; item += WARP_CL_THREADS) {
+        const int p = item / chunks, c = (item - p * chunks) * VEC;
+        const int i = wb.i0 + p / WARP_TW, j = wb.j0 + p % WARP_TW;
+        if (i >= H || j >= W) continue;
+        const WarpTexel<float> t = tex[p];
+        uint4 o = make_uint4(0u, 0u, 0u, 0u);
+        if (t.valid) {
+            const uint16_t *sp = view + (int64_t)t.o00 * Cn + c;
+            float a[8], b[8], cc[8], d[8], r[8];
+            up8<C>(load8_or_zero(sp, t.valid & 1, view), a);
+            up8<C>(load8_or_zero(sp + Cn, t.valid & 2, view), b);
+            up8<C>(load8_or_zero(sp + rowC, t.valid & 4, view), cc);
+            up8<C>(load8_or_zero(sp + rowC + Cn, t.valid & 8, view), d);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r[k] = t.w00 * a[k] + t.w01 * b[k] + t.w10 * cc[k] + t.w11 * d[k];
+            o = down8<C>(r);
+        }
+        *reinterpret_cast<uint4 *>(dst + (((int64_t)n * H + i) * W + j) * Cn + c) = o;
+    }
+}
+
+// The other three layout combinations (and channel counts / alignments the kernel above does not take): warp_fwd's mapping,
+// an 8 x 8 tile of destination pixels x up to 64 channels split over the four waves, with 2-byte accesses through the
+// element strides of either layout.
+template <typename C>
+__global__ __launch_bounds__(WARP_PIX *WARP_SUB) void warp_fwd_half(
+    const uint16_t *__restrict__ src, const float *__restrict__ Mv, int N, int Cn, int h, int w, int H, int W,
+    int nearest, int src_nhwc, int dst_nhwc, uint16_t *__restrict__ dst)
+{
+    __shared__ WarpTexel<float> tex[WARP_PIX];
+    const int lane = threadIdx.x & (WARP_PIX - 1);
+    const int sub = threadIdx.x / WARP_PIX;
+    WarpBlock wb;
+    if (!warp_block(N, H, W, (Cn + WARP_CH - 1) / WARP_CH, wb)) return;
+    const int n = wb.n, i = wb.i0 + lane / WARP_TW, j = wb.j0 + lane % WARP_TW;
+    const bool live = i < H && j < W;
+    if (sub == 0) tex[lane] = warp_texel(Mv + (int64_t)n * 9, i, j, h, w, live, nearest);
+    __syncthreads();
+    if (!live) return;
+    const WarpTexel<float> t = tex[lane];
+    constexpr int CPT = WARP_CH / WARP_SUB;
+    const int64_t plane = (int64_t)h * w, oplane = (int64_t)H * W;
+    const int64_t s_c = src_nhwc ? 1 : plane, s_t = src_nhwc ? Cn : 1;            // element strides: channel, texel
+    const int64_t d_c = dst_nhwc ? 1 : oplane, d_p = dst_nhwc ? Cn : 1;
+    const uint16_t *view = src + (int64_t)n * Cn * plane + (int64_t)t.o00 * s_t;
+    uint16_t *op = dst + (int64_t)n * Cn * oplane + ((int64_t)i * W + j) * d_p;
+    const int c_begin = wb.group * WARP_CH + sub * CPT, c_end = min(Cn, c_begin + CPT);
+    for (int c = c_begin; c < c_end; ++c) {
+        uint16_t o = 0;
+        if (t.valid) {
+            const uint16_t *sp = view + c * s_c;
+            const float a = (t.valid & 1) ? C::up(sp[0]) : 0.f, b = (t.valid & 2) ? C::up(sp[s_t]) : 0.f;
+            const float cc = (t.valid & 4) ? C::up(sp[w * s_t]) : 0.f, d = (t.valid & 8) ? C::up(sp[w * s_t + s_t]) : 0.f;
+            o = C::down(t.w00 * a + t.w01 * b + t.w10 * cc + t.w11 * d);
+        }
+        op[c * d_c] = o;
+    }
+}
+
+template <typename C>
+static int warp_half_entry(void *stream, const uint16_t *a, const float *Mv, int N, int Cn, int h, int w, int H, int W, int nhwc,
+                           uint16_t *o)
+{
+    if (N < 0 || Cn < 0 || h <= 0 || w <= 0 || H < 0 || W < 0) return (int)hipErrorInvalidValue;
+    if (nhwc & ~7) return (int)hipErrorInvalidValue;
+    if ((int64_t)N * H * W == 0 || Cn == 0) return 0;
+    if (!a || !Mv || !o) return (int)hipErrorInvalidValue;
+    if ((int64_t)h * w > 0x7fffffffLL) return (int)hipErrorInvalidValue;         // (a texel offset is an int)
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nearest = (nhwc >> 2) & 1;
+    nhwc &= 3;
+    if (nhwc == 3 && Cn % 8 == 0 && aligned(a, 16) && aligned(o, 16) && (int64_t)h * w * Cn <= 0x7fffffffLL) {
+        const int64_t nb = warp_grid(N, H, W, 1);
+        if (nb > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL((warp_fwd_cl_half<C>), dim3((unsigned)nb), dim3(WARP_CL_THREADS), 0, st, a, Mv, N, Cn, h, w, H, W, nearest, o);
+        g_warp_last_kernel = "warp_fwd_cl_half";
+        return (int)hipGetLastError();
+    }
+    const int64_t blocks = warp_grid(N, H, W, (Cn + WARP_CH - 1) / WARP_CH);
+    if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((warp_fwd_half<C>), dim3((unsigned)blocks), dim3(WARP_PIX * WARP_SUB), 0, st, a, Mv, N, Cn, h, w, H, W, nearest,
+                       (nhwc >> 1) & 1, nhwc & 1, o);
+    g_warp_last_kernel = "warp_fwd_half";
+    return (int)hipGetLastError();
+}
+
 // [n, rows, cols] -> [n, cols, rows] through a 64 x 64 LDS tile (reads and writes both in 256-byte runs): turns an NCHW
 // feature map into the channel-last layout the fast warp kernels read (rows = C, cols = h*w) and back
 // (rows = h*w, cols = C).
@@ -1429,6 +1541,18 @@ int mvdetr_warp_perspective_forward_f64(void *stream, const double *src, const d
 {
     return mvdetr::warp_entry<double>(false, stream, src, M, n, channels, src_h, src_w, dst_h, dst_w,
                                       layout_nhwc, dst);
+}
+
+int mvdetr_warp_perspective_forward_f16(void *stream, const uint16_t *src, const float *M, int n, int channels, int src_h,
+                                        int src_w, int dst_h, int dst_w, int layout_nhwc, uint16_t *dst)
+{
+    return mvdetr::warp_half_entry<mvdetr::F16>(stream, src, M, n, channels, src_h, src_w, dst_h, dst_w, layout_nhwc, dst);
+}
+
+int mvdetr_warp_perspective_forward_bf16(void *stream, const uint16_t *src, const float *M, int n, int channels, int src_h,
+                                         int src_w, int dst_h, int dst_w, int layout_nhwc, uint16_t *dst)
+{
+    return mvdetr::warp_half_entry<mvdetr::BF16>(stream, src, M, n, channels, src_h, src_w, dst_h, dst_w, layout_nhwc, dst);
 }
 
 int mvdetr_warp_perspective_backward_f32(void *stream, const float *grad_dst, const float *M, int n,

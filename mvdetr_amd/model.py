@@ -191,6 +191,7 @@ class MVDeTr(nn.Module):
         self.Rimg_shape, self.Rworld_shape = geom.Rimg_shape, geom.Rworld_shape
         self.img_reduce, self.num_cam = geom.img_reduce, geom.num_cam
         self.channels_last = channels_last
+        self.compute_dtype = None                                          # set by to_inference(): float16 / bfloat16
         bottleneck_dim = geom.feat_channels if bottleneck_dim is None else bottleneck_dim
         # image pixel -> reduced world grid, fp64 (mvdetr.py:82-95)
         self.register_buffer("proj_mats", torch.from_numpy(geometry.build_proj_mats(geom, Ks, Rts, z)), persistent=False)
@@ -272,8 +273,48 @@ class MVDeTr(nn.Module):
             new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
+    def to_inference(self, dtype):
+        """Convert the model for 16-bit INFERENCE (``dtype`` = torch.float16 or torch.bfloat16; forward only, under
+        ``no_grad``) and return it, in eval mode.  What ``nn.Module.half()`` would get wrong is left alone:
+
+          * convolution, linear, LayerNorm and embedding parameters and the position embedding (the ``conv`` aggregator's
+            coordinate map likewise) are cast to ``dtype``: the trunk's and the heads' convolutions and the encoder's GEMMs
+            run on the matrix units in 16 bits;
+          * BatchNorm2d parameters and running statistics stay float32 (torch's batch norm takes 16-bit activations with
+            float32 statistics);
+          * ``proj_mats`` (float64) and the encoder's ``reference_points`` / ``reference_shared`` (float32) are not touched,
+            bit for bit: a [0, 1] coordinate in bfloat16 is +-0.7 px on a 180-wide map.  ``frame_proj_mats`` stays float32.
+
+        The warp (fp32 matrices, fp64 source positions), the fused deformable attention (fp32 reference points, softmax and
+        locations) and the add + LayerNorm tails (fp32 statistics) run their 16-bit-storage HIP kernels, each rounding once
+        on the way out; the trunk's BatchNorm / ReLU / max-pool run as torch's ops (their fused epilogues are float32).
+        ``forward`` then returns 16-bit head maps; ``detect`` upcasts the two world maps for the detection extraction.
+        Served for the ``deform_trans`` and ``conv`` world features; training, ``torch.autocast`` and the backward are not
+        part of it."""
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("to_inference: dtype must be torch.float16 or torch.bfloat16")
+        if self.world_feat_arch in ("deform_conv", "trans"):
+            raise NotImplementedError(f"to_inference: the '{self.world_feat_arch}' world feature's ops (deformable convolution, "
+                                      "fused attention) are float32 / float64 only; 'deform_trans' and 'conv' convert")
+        self.eval()
+        for m in self.modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                continue
+            for p in m._parameters.values():
+                if p is not None and p.is_floating_point():
+                    p.data = p.data.to(dtype)
+            if hasattr(m, "cache_fused_projection"):
+                m._fused_cache = None                                      # (a cached permuted weight has the old dtype)
+        for name in ("pos_embedding", "coord_map"):
+            if name in self.world_feat._buffers and self.world_feat._buffers[name] is not None:
+                self.world_feat._buffers[name] = self.world_feat._buffers[name].to(dtype)
+        self.compute_dtype = dtype
+        return self
+
     def features(self, imgs):
         B, N, C, H, W = imgs.shape
+        if self.compute_dtype is not None:
+            imgs = imgs.to(self.compute_dtype)
         x = imgs.reshape(B * N, C, H, W)
         if self.channels_last:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -301,6 +342,9 @@ class MVDeTr(nn.Module):
         with torch.no_grad():
             (world_heatmap, world_offset), _ = self(imgs, M)
         detect_kw.setdefault("world_reduce", self.geom.world_reduce)
+        if self.compute_dtype is not None:
+            # 16-bit inference: the extraction is float32 / float64 (thresholds, positions); two small maps are upcast
+            world_heatmap, world_offset = world_heatmap.float(), world_offset.float()
         return bev_detect(world_heatmap, world_offset, **detect_kw)
 
     def hot_path(self, feat, proj):

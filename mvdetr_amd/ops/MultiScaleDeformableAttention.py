@@ -203,6 +203,47 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, level_start_index, refer
     return out
 
 
+def fused_half_supported(value, num_levels, num_query, num_point) -> bool:
+    """True when ms_deform_attn_forward_fused_half takes a call with this ``value`` (CUDA float16 / bfloat16
+    [B, S, M, D]): 16- or 32-channel heads, 4 points, at most 16 levels, queries = tokens.  Equal level shapes are the
+    caller's to check (device data)."""
+    if not value.is_cuda or value.dtype not in (torch.float16, torch.bfloat16) or value.dim() != 4:
+        return False
+    return bool(_lib.lib().mvdetr_msda_fused_half_supported(*value.shape, num_levels, num_query, num_point))
+
+
+def ms_deform_attn_forward_fused_half(value, spatial_shapes, level_start_index, reference_points_fp32, raw):
+    """The fused inference forward in 16-bit storage (csrc/msda_forward_fused_half.hip): ``value`` [B, S, M, D] and ``raw``
+    [B, S, >= M*L*12] (the module's ONE GEMM output, slice_major_rows(level_outer=True)) in float16 or bfloat16;
+    ``reference_points_fp32`` [B or 1, L, S, 2] in FLOAT32, one point per (query, level), level-major -- a [0, 1]
+    coordinate does not survive 16 bits.  Softmax, locations and the blend are fp32 in the kernel; -> [B, S, M*D] in
+    value's dtype, each element rounded once.  The levels must have equal shapes (else the result is NaN)."""
+    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index)])
+    if value.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("ms_deform_attn_forward_fused_half: value must be float16 or bfloat16")
+    B, S, M, D = value.shape
+    L = spatial_shapes.shape[0]
+    ref = reference_points_fp32
+    if (not ref.is_cuda or ref.dtype != torch.float32 or ref.dim() != 4 or tuple(ref.shape[1:]) != (L, S, 2)
+            or ref.shape[0] not in (1, B)):
+        raise RuntimeError("reference_points_fp32 must be a CUDA float32 tensor [B or 1, L, Lq, 2]: one point per "
+                           "(query, level), level-major")
+    if (raw.dim() != 3 or raw.shape[0] != B or raw.shape[1] != S or raw.shape[2] < M * L * 12 or not raw.is_cuda
+            or raw.dtype != value.dtype or raw.stride(2) != 1 or (B > 1 and raw.stride(0) != raw.stride(1) * S)):
+        raise RuntimeError("raw must be a CUDA tensor [B, Lq, >= M*L*P*3] of value's dtype, dense per query")
+    if not ref[0].is_contiguous():
+        ref = ref.contiguous()
+    rstride = ref.stride(0) if ref.shape[0] > 1 else 0
+    _meta(spatial_shapes, value.device), _meta(level_start_index, value.device)
+    out = torch.empty((B, S, M * D), dtype=value.dtype, device=value.device)
+    with torch.cuda.device(value.device):
+        rc = getattr(_lib.lib(), f"mvdetr_msda_forward_fused_{_lib.suffix(value.dtype, half_ok=True)}")(
+            _lib.current_stream_ptr(value.device), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+            ref.data_ptr(), rstride, raw.data_ptr(), raw.stride(1), B, S, M, D, L, 4, out.data_ptr())
+    _lib.check(rc, "ms_deform_attn_forward_fused_half")
+    return out
+
+
 def fused_train_supported(B, S, M, D, num_levels, num_query, num_point) -> bool:
     """True when the fused TRAINING pair takes a call of these dimensions (CUDA fp32 tensors, equal level shapes and one
     reference point per (query, level) are the caller's to check): include/mvdetr_ops.h."""

@@ -238,6 +238,27 @@ class MSDeformAttn(nn.Module):
                                         input_level_start_index, N, Len_q)
         if pending is not None:
             value = pending()
+        if (self.fused_inference and self.raw_level_outer and not needs_grad and query_levels is None
+                and query.is_cuda and query.dtype in (torch.float16, torch.bfloat16)
+                and value.is_cuda and value.dtype == query.dtype
+                and reference_points.dim() == 5 and reference_points.shape[-1] == 2
+                and MSDA.fused_half_supported(value.view(N, Len_in, M, D), self.n_levels, Len_q, self.n_points)
+                and self._levels_equal(input_spatial_shapes)):
+            # 16-bit inference: the same ONE permuted GEMM for offsets + logits, then the 16-bit fused kernel on the FP32
+            # reference map (a [0, 1] coordinate in bfloat16 is +-0.7 px on a 180-wide map: it is never rounded)
+            shared = shared_reference
+            if shared is None and reference_points.is_cuda and reference_points.dtype == torch.float32:
+                shared = self._shared_reference(reference_points)
+            if shared is not None and shared.is_cuda and shared.dtype == torch.float32:
+                w, b = self._fused_projection()
+                raw = F.linear(query, w, b)
+                value4 = value.view(N, Len_in, M, D).contiguous()
+                shared = shared.contiguous()
+                if (raw.dtype == value4.dtype and value4.data_ptr() % 16 == 0 and raw.data_ptr() % 16 == 0
+                        and shared.data_ptr() % 8 == 0):
+                    out = MSDA.ms_deform_attn_forward_fused_half(value4, input_spatial_shapes, input_level_start_index,
+                                                                 shared, raw)
+                    return self.output_proj(out)
         if (needs_grad and self.fused_training and self.raw_level_outer and query_levels is None and self.n_points == 4
                 and reference_points.dim() == 5 and reference_points.shape[-1] == 2
                 and query.is_cuda and query.dtype == torch.float32 and value.is_cuda and value.dtype == torch.float32
@@ -274,6 +295,12 @@ class MSDeformAttn(nn.Module):
                         input_level_start_index, N, Len_q):
         """ms_deform_attn.py:100-117 from the raw offsets / logits on: softmax, sampling locations, the extension's
         differentiable function, output projection."""
+        half = value.dtype in (torch.float16, torch.bfloat16)
+        if half:
+            # 16-bit calls the fused 16-bit kernel does not take: the core runs in fp32 on the upcast value, fp32 locations
+            # (formed from the reference points as they are -- never rounded to 16 bits) and fp32 weights
+            offsets, weights = offsets.float(), weights.float()
+            reference_points = reference_points.float()
         weights = F.softmax(weights, -1).view(N, Len_q, self.n_heads, self.n_levels, self.n_points)
         if reference_points.shape[-1] == 2:
             normalizer = torch.stack([input_spatial_shapes[..., 1], input_spatial_shapes[..., 0]], -1)
@@ -285,6 +312,10 @@ class MSDeformAttn(nn.Module):
         else:
             raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead."
                              .format(reference_points.shape[-1]))
+        if half:
+            out = MSDeformAttnFunction.apply(value.float().contiguous(), input_spatial_shapes, input_level_start_index,
+                                             locations.contiguous(), weights.contiguous(), self.im2col_step)
+            return self.output_proj(out.to(value.dtype))
         out = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                          locations.contiguous(), weights, self.im2col_step)
         return self.output_proj(out)

@@ -17,6 +17,7 @@ from .. import _lib
 
 
 DST_NHWC, SRC_NHWC, NEAREST = 1, 2, 4          # bits of the C ABI's layout_nhwc argument (include/mvdetr_ops.h)
+HALF_DTYPES = (torch.float16, torch.bfloat16)  # 16-bit storage: inference only (device forward, fp32 matrices)
 
 
 def _launch(name, a, M, n, c, h, w, H, W, layout, out, plan=None, tag=0):
@@ -43,7 +44,8 @@ def _launch(name, a, M, n, c, h, w, H, W, layout, out, plan=None, tag=0):
         _lib.check(rc, f"warp_perspective_{name} (host)")
         return
     with torch.cuda.device(a.device):
-        rc = getattr(_lib.lib(), f"mvdetr_warp_perspective_{name}_{_lib.suffix(a.dtype)}")(
+        # float16 / bfloat16: device forward only (16-bit storage, fp32 matrices and arithmetic; include/mvdetr_ops.h)
+        rc = getattr(_lib.lib(), f"mvdetr_warp_perspective_{name}_{_lib.suffix(a.dtype, half_ok=name == 'forward')}")(
             _lib.current_stream_ptr(a.device), a.data_ptr(), M.data_ptr(), n, c, h, w, H, W, layout,
             out.data_ptr())
     _lib.check(rc, f"warp_perspective_{name}")
@@ -76,10 +78,10 @@ def release_scratch() -> None:
 
 def _channel_last_source(src, channels_last_out):
     """True when ``src`` ([N,C,h,w] shape) already lies in memory as [N,h,w,C] and a channel-last kernel takes it
-    (NHWC destination: any float dtype; NCHW destination: float32): then the warp reads it in place instead of
-    copying it to NCHW first."""
+    (NHWC destination: any float dtype; NCHW destination: float32 and the 16-bit types): then the warp reads it in place
+    instead of copying it to NCHW first."""
     n, c, h, w = src.shape
-    return ((channels_last_out or src.dtype == torch.float32) and src.is_cuda and c > 1 and h * w > 1
+    return ((channels_last_out or src.dtype == torch.float32 or src.dtype in HALF_DTYPES) and src.is_cuda and c > 1 and h * w > 1
             and src.is_contiguous(memory_format=torch.channels_last)
             and not src.is_contiguous() and (c * src.element_size()) % 16 == 0 and src.data_ptr() % 16 == 0)
 
@@ -159,7 +161,7 @@ class WarpPerspectiveFunction(Function):
         _channel_last_source_flag = src_cl                         # the caller's own layout (the gradient's layout)
         if not src_cl:
             src = src.contiguous()
-            if (channels_last_out and src.is_cuda and c > 1 and h * w > 1
+            if (channels_last_out and src.is_cuda and c > 1 and h * w > 1 and src.dtype not in HALF_DTYPES
                     and (c * src.element_size()) % 16 == 0 and h * w * c < 2 ** 31 and n <= 65535):
                 # an NCHW source for a channel-last destination: one tiled transpose (reads and writes in 256-byte runs)
                 # and the channel-last kernel, instead of the NCHW kernel's 4-byte gathers (92 -> 56 us at Wildtrack
@@ -216,6 +218,7 @@ def warp_perspective(src, M, dsize, mode="bilinear", padding_mode="zeros", align
     Modes: 'bilinear' (the model, mvdetr.py:194) and 'nearest' (the dataset's ground-plane masks,
     frameDataset.py:80); zero padding and align_corners=False only, the configuration the reference uses.
     CPU tensors run on the library's own host implementation (the reference has none; kornia does).
+    CUDA float16 / bfloat16 ``src`` (inference): ``M`` is used in float32, the result has ``src``'s dtype; no gradient.
     """
     if mode not in ("bilinear", "nearest") or padding_mode != "zeros" or align_corners not in (False, None):
         raise NotImplementedError(
@@ -224,6 +227,17 @@ def warp_perspective(src, M, dsize, mode="bilinear", padding_mode="zeros", align
     if src.dim() != 4 or M.shape[-2:] != (3, 3) or M.reshape(-1, 3, 3).shape[0] != src.shape[0]:
         raise ValueError(f"warp_perspective: expected src [N,C,h,w] and M [N,3,3], got "
                          f"{tuple(src.shape)} and {tuple(M.shape)}")
+    if src.dtype in HALF_DTYPES:
+        # 16-bit storage, inference only: the matrices stay fp32 (a projection matrix in bfloat16 is pixels off) and the
+        # kernel computes the source position in fp64 and the blend in fp32, like the fp32 op
+        if not src.is_cuda:
+            raise RuntimeError("warp_perspective: float16 / bfloat16 features are implemented on the GPU only "
+                               "(CPU tensors: float32 or float64 features)")
+        if src.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("warp_perspective: float16 / bfloat16 features are forward-only (inference); "
+                               "there is no 16-bit backward -- run under torch.no_grad() or train in float32")
+        M = M.reshape(-1, 3, 3).to(device=src.device, dtype=torch.float32).contiguous()
+        return WarpPerspectiveFunction.apply(src, M, tuple(dsize), bool(channels_last_out), mode == "nearest")
     if src.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("warp_perspective: float32 or float64 features")
     M = M.reshape(-1, 3, 3).to(device=src.device, dtype=src.dtype).contiguous()

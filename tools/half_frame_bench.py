@@ -1,0 +1,175 @@
+"""fp32 against 16-bit inference (MVDeTr.to_inference) at Wildtrack shape, in ONE process, the variants alternated
+repetition by repetition (same call, alternating, spread first):
+
+  detect          a whole frame, images -> ground-plane detections (MVDeTr.detect);
+  hot_path        warp + shadow transformer on precomputed trunk features (MVDeTr.hot_path);
+  warp            ops.warp_perspective alone, channel-last -> channel-last (warp_fwd_cl / warp_fwd_cl_half);
+  msda            the fused deformable-attention forward alone on the encoder's input
+                  (msda_fwd_group2 / msda_fwd_fused_half);
+  add_layernorm   ops.add_layer_norm alone with the second output, 75,600 rows x 128;
+
+each for float32, bfloat16 and float16.
+
+    python tools/half_frame_bench.py [--reps N] [--config wildtrack]
+
+Clock: device events around the enqueued work, one repetition at a time.  Per row: median, the 10th and 90th percentile, min
+and max of N repetitions after warm-up.  `spread` is the float32 variant's own p90 - p10 in that row; a 16-bit variant is
+`faster` when its median is below float32's by more than that spread, `same` within it, `SLOWER` above it.  Also reports,
+on one seeded frame, how many detections differ between float32 and each 16-bit run (information, not a bar: the weights
+are seeded random, the threshold is set so that float32 keeps a few hundred candidates).  Prints one JSON line per row and
+a table."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from mvdetr_amd.model import build_model  # noqa: E402
+from mvdetr_amd.ops import MultiScaleDeformableAttention as MSDA  # noqa: E402
+from mvdetr_amd.ops import add_layer_norm, warp_perspective  # noqa: E402
+from mvdetr_amd.ops import warp as warp_mod  # noqa: E402
+
+DEV = "cuda:0"
+VARIANTS = {"float32": None, "bfloat16": torch.bfloat16, "float16": torch.float16}
+
+
+def perturb_sampling(model, std_px=1.5, seed=1234):
+    """Seeded stand-in for learned sampling offsets / attention logits (the reference initialises both projections' weights
+    to zero, which makes every query sample the same pattern): the benchmark's own recipe."""
+    g = torch.Generator().manual_seed(seed)
+    for layer in model.world_feat.encoder.layers:
+        at = layer.self_attn
+        with torch.no_grad():
+            at.sampling_offsets.weight.copy_(torch.randn(at.sampling_offsets.weight.shape, generator=g) * (std_px / (1.4 * at.d_model ** 0.5)))
+            at.attention_weights.weight.copy_(torch.randn(at.attention_weights.weight.shape, generator=g) * (1.0 / (1.4 * at.d_model ** 0.5)))
+
+
+def alternated(fns, reps, warmup=3):
+    """{variant: device-event times in us}, the variants taking turns inside every repetition."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {n: [] for n in fns}
+    for _ in range(reps):
+        for n, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[n].append(a.elapsed_time(b) * 1e3)
+    return times
+
+
+def stats(t):
+    s = sorted(t)
+    pick = lambda q: s[min(len(s) - 1, int(q * (len(s) - 1) + 0.5))]  # noqa: E731
+    return {"median_us": pick(0.5), "p10_us": pick(0.1), "p90_us": pick(0.9), "min_us": s[0], "max_us": s[-1]}
+
+
+def detection_cells(model, imgs, M, thres):
+    det = model.detect(imgs, M, cls_thres=thres)
+    n = int(det.count[0])
+    return set(det.cell[0, :min(n, det.cell.shape[1])].tolist())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--config", default="wildtrack")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("half_frame_bench: needs a GPU (no CPU fallback for timings)")
+    from helpers import fused_train_inputs
+    print(f"# device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; config {a.config}; {a.reps} alternated "
+          f"repetitions per row, device events", flush=True)
+
+    models = {}
+    for name, dtype in VARIANTS.items():
+        m = build_model(a.config, seed=0)
+        perturb_sampling(m)
+        m = m.to(DEV).eval()
+        models[name] = m if dtype is None else m.to_inference(dtype)
+    ref_model = models["float32"]
+    N, (Hi, Wi), (H, W) = ref_model.num_cam, ref_model.geom.img_shape, ref_model.Rworld_shape
+    imgs = torch.randn(1, N, 3, Hi, Wi, generator=torch.Generator().manual_seed(1000)).to(DEV)
+    M = torch.eye(3).repeat(1, N, 1, 1)
+
+    wf = ref_model.world_feat
+    C, heads = wf.hidden_dim, 8
+    h, w = H // wf.stride, W // wf.stride
+    S = N * h * w
+    value, shapes, lsi, ref_lm, raw, _ = [x.to(DEV) for x in fused_train_inputs(N, h, w, heads, C // heads, 4, seed=0)]
+    g = torch.Generator().manual_seed(7)
+    ln_x, ln_res, ln_pos = (torch.randn(b, S, C, generator=g).to(DEV) for b in (1, 1, 1))
+
+    fns = {k: {} for k in ("detect", "hot_path", "warp", "msda", "add_layernorm")}
+    kernels = {k: {} for k in fns}
+    with torch.no_grad():
+        for name, dtype in VARIANTS.items():
+            model = models[name]
+            feat = model.features(imgs)
+            proj = model.frame_proj_mats(M, DEV)
+            cast = (lambda t: t) if dtype is None else (lambda t, d=dtype: t.to(d))
+            v_, raw_ = cast(value), cast(raw)
+            x_, res_, pos_ = cast(ln_x), cast(ln_res), cast(ln_pos)
+            norm = model.world_feat.encoder.layers[0].norm2
+            fns["detect"][name] = lambda model=model: model.detect(imgs, M)
+            fns["hot_path"][name] = lambda model=model, feat=feat, proj=proj: model.hot_path(feat, proj)
+            fns["warp"][name] = lambda feat=feat, proj=proj: warp_perspective(feat, proj, (H, W), channels_last_out=True)
+            if dtype is None:
+                fns["msda"][name] = lambda v_=v_, raw_=raw_: MSDA.ms_deform_attn_forward_fused(
+                    v_, shapes, lsi, ref_lm, None, None, raw=raw_, ref_level_major=True, raw_level_outer=True)
+            else:
+                fns["msda"][name] = lambda v_=v_, raw_=raw_: MSDA.ms_deform_attn_forward_fused_half(v_, shapes, lsi, ref_lm, raw_)
+            fns["add_layernorm"][name] = lambda x_=x_, res_=res_, pos_=pos_, norm=norm: add_layer_norm(x_, res_, norm, then_add=pos_)
+            # which kernels the variant runs (asked once, outside the timed window)
+            fns["warp"][name]()
+            kernels["warp"][name] = warp_mod.last_kernel()
+            fns["msda"][name]()
+            kernels["msda"][name] = MSDA.last_forward_kernel()
+            fns["hot_path"][name]()
+            kernels["hot_path"][name] = f"{warp_mod.last_kernel()} + {MSDA.last_forward_kernel()}"
+
+        rows = []
+        for what, variants in fns.items():
+            res = {n: stats(t) for n, t in alternated(variants, a.reps).items()}
+            base = res["float32"]
+            spread = base["p90_us"] - base["p10_us"]
+            for n, r in res.items():
+                d = r["median_us"] - base["median_us"]
+                verdict = "baseline" if n == "float32" else "faster" if -d > spread else "same" if d <= spread else "SLOWER"
+                row = {"what": what, "variant": n, **{k: round(v, 1) for k, v in r.items()}, "fp32_spread_us": round(spread, 1),
+                       "ratio_to_fp32": round(r["median_us"] / base["median_us"], 3), "verdict": verdict,
+                       "kernel": kernels[what].get(n, "")}
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+
+        # detections on one seeded frame: the threshold at which float32 keeps its 300 best-scoring cells as candidates
+        (hm, _), _ = ref_model(imgs, M)
+        thres = float(torch.sigmoid(hm.float()).flatten().topk(300).values[-1])
+        cells = {n: detection_cells(m, imgs, M, thres) for n, m in models.items()}
+        for n in ("bfloat16", "float16"):
+            row = {"what": "detections", "variant": n, "cls_thres": round(thres, 5), "kept_fp32": len(cells["float32"]),
+                   "kept": len(cells[n]), "only_fp32": len(cells["float32"] - cells[n]), "only_16bit": len(cells[n] - cells["float32"])}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+
+    print(f"\n{'what':<14} {'variant':<9} {'median us':>10} {'p10':>10} {'p90':>10} {'min':>10} {'max':>10} {'fp32 spread':>12} {'/ fp32':>7}  verdict   kernel")
+    for r in rows:
+        if r["what"] == "detections":
+            print(f"{'detections':<14} {r['variant']:<9} kept by float32 {r['kept_fp32']}, by {r['variant']} {r['kept']}; only in float32 "
+                  f"{r['only_fp32']}, only in {r['variant']} {r['only_16bit']} (cls_thres {r['cls_thres']})")
+            continue
+        print(f"{r['what']:<14} {r['variant']:<9} {r['median_us']:>10.1f} {r['p10_us']:>10.1f} {r['p90_us']:>10.1f} {r['min_us']:>10.1f} "
+              f"{r['max_us']:>10.1f} {r['fp32_spread_us']:>12.1f} {r['ratio_to_fp32']:>7.3f}  {r['verdict']:<9} {r['kernel']}")
+
+
+if __name__ == "__main__":
+    main()
