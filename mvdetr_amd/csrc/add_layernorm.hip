@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256) void add_layernorm_rows128x2(const float *__re
     }
 }
 
-// 16-bit storage (float16 / bfloat16; inference): x, residual, gamma, beta, add2, out and out2 are 16-bit words, the sum
-// x + residual, its mean and variance and the normalised row are fp32, and each output element is rounded once -- out2 from
+// 16-bit storage (float16 / bfloat16; inference): x, residual, gamma, beta, add2, out and out2 are 16-bit words, the
+// centred row (x - mean) + residual, its variance and the normalised row are fp32, and each output element is rounded once -- out2 from
 // the UNROUNDED y + add2.  A lane holds VEC consecutive channels (VEC = 8: one 16-byte access, COLS / 8 lanes per row and
 // 512 / COLS rows per wave; VEC = COLS / 64: one row per wave, for tensors that are not 16-byte aligned); the sums are
 // xor-shuffles among the lanes of a row.
@@ -142,23 +142,34 @@ __global__ __launch_bounds__(256) void add_layernorm_rows_half(const uint16_t *_
         const bool live = r < rows;                           // (the last wave's upper rows idle, converged for the shuffles)
         const int64_t rr = live ? r : rows - 1;
         const Raw<VEC> xr = *reinterpret_cast<const Raw<VEC> *>(x + rr * COLS + sub * VEC);
-        float v[VEC];
+        // The centred row is formed WITHOUT forming x + residual: on a row whose mean is large against its spread (mean 1000,
+        // unit spread) the fp32 rounding of that sum (2^-24 of the magnitude) and of the row's total would be 1e-4 of the
+        // normalised element.  mean0 is the rounded total / COLS; (x - mean0) cancels exactly where it matters and takes the
+        // residual at the spread's scale; a second reduction over these registers removes what mean0 was off.
+        float v[VEC], q[VEC];
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) v[i] = C::up(xr.v[i]);
+        for (int i = 0; i < VEC; ++i) { v[i] = C::up(xr.v[i]); q[i] = 0.f; }
         if (res) {
-            const Raw<VEC> q = *reinterpret_cast<const Raw<VEC> *>(res + rr * COLS + sub * VEC);
+            const Raw<VEC> qr = *reinterpret_cast<const Raw<VEC> *>(res + rr * COLS + sub * VEC);
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) v[i] += C::up(q.v[i]);
+            for (int i = 0; i < VEC; ++i) q[i] = C::up(qr.v[i]);
         }
-        float s = 0.f;
+        float s = 0.f, sq = 0.f;
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) s += v[i];
+        for (int i = 0; i < VEC; ++i) { s += v[i]; sq += q[i]; }
+        s += sq;
 #pragma unroll
         for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        const float mean = s * (1.f / COLS);
+        const float mean0 = s * (1.f / COLS);
+        float cs = 0.f;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { v[i] = (v[i] - mean0) + q[i]; cs += v[i]; }
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) cs += __shfl_xor(cs, o, 64);
+        const float shift = cs * (1.f / COLS);
         float m2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) m2 += (v[i] - mean) * (v[i] - mean);
+        for (int i = 0; i < VEC; ++i) { v[i] -= shift; m2 += v[i] * v[i]; }
 #pragma unroll
         for (int o = LPR / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
         const float rstd = rsqrtf(m2 * (1.f / COLS) + eps);
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(256) void add_layernorm_rows_half(const uint16_t *_
         Raw<VEC> yo;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-            y[i] = (v[i] - mean) * rstd * g[i] + bt[i];
+            y[i] = v[i] * rstd * g[i] + bt[i];
             yo.v[i] = C::down(y[i]);
         }
         if (live) *reinterpret_cast<Raw<VEC> *>(out + r * COLS + sub * VEC) = yo;

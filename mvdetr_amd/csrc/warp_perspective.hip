@@ -1322,6 +1322,13 @@ static int warp_entry(bool backward, void *stream, const T *a, const T *Mv, int 
 // blend weights and the blend are fp32 (WarpTexel<float>: storage type and compute type are separate here), and every
 // output element is rounded once, to nearest-even.  warp_fwd_cl_half is warp_fwd_cl with 8 channels (16 bytes) per lane:
 // channel-last on both sides, the layout a channels_last trunk hands to the shadow transformer.
+// The blend of both 16-bit kernels in ONE order of fused multiply-adds (under -ffp-contract=fast the compiler picks an order
+// per kernel): the result of a call does not depend on which of the two its layout and alignment select.
+__device__ __forceinline__ float warp_blend_half(float w00, float a, float w01, float b, float w10, float c, float w11, float d)
+{
+    return fmaf(w11, d, fmaf(w10, c, fmaf(w01, b, w00 * a)));
+}
+
 template <typename C>
 __global__ __launch_bounds__(WARP_CL_THREADS) void warp_fwd_cl_half(
     const uint16_t *__restrict__ src, const float *__restrict__ Mv, int N, int Cn, int h, int w, int H, int W,
@@ -1354,7 +1361,7 @@ __global__ __launch_bounds__(WARP_CL_THREADS) void warp_fwd_cl_half(
             up8<C>(load8_or_zero(sp + rowC, t.valid & 4, view), cc);
             up8<C>(load8_or_zero(sp + rowC + Cn, t.valid & 8, view), d);
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) r[k] = t.w00 * a[k] + t.w01 * b[k] + t.w10 * cc[k] + t.w11 * d[k];
+            for (int k = 0; k < VEC; ++k) r[k] = warp_blend_half(t.w00, a[k], t.w01, b[k], t.w10, cc[k], t.w11, d[k]);
             o = down8<C>(r);
         }
         *reinterpret_cast<uint4 *>(dst + (((int64_t)n * H + i) * W + j) * Cn + c) = o;
@@ -1393,7 +1400,7 @@ __global__ __launch_bounds__(WARP_PIX *WARP_SUB) void warp_fwd_half(
             const uint16_t *sp = view + c * s_c;
             const float a = (t.valid & 1) ? C::up(sp[0]) : 0.f, b = (t.valid & 2) ? C::up(sp[s_t]) : 0.f;
             const float cc = (t.valid & 4) ? C::up(sp[w * s_t]) : 0.f, d = (t.valid & 8) ? C::up(sp[w * s_t + s_t]) : 0.f;
-            o = C::down(t.w00 * a + t.w01 * b + t.w10 * cc + t.w11 * d);
+            o = C::down(warp_blend_half(t.w00, a, t.w01, b, t.w10, cc, t.w11, d));
         }
         op[c * d_c] = o;
     }

@@ -36,17 +36,22 @@ def add_layer_norm(x: torch.Tensor, residual: torch.Tensor, norm: torch.nn.Layer
     if then_add is not None:
         fused = fused and (then_add.is_cuda and then_add.dtype == x.dtype and then_add.dim() == x.dim() == 3
                            and then_add.shape[1:] == x.shape[1:] and then_add.shape[0] in (1, x.shape[0]))
+    if fused:
+        xc = x.contiguous()
+        rc = None if residual is None else residual.to(x.dtype).contiguous()
+        w = norm.weight.detach().contiguous() if norm.weight is not None else None
+        b = norm.bias.detach().contiguous() if norm.bias is not None else None
+        a2 = None if then_add is None else then_add.contiguous()
+        cols = xc.shape[-1]
+        # a lane reads its cols / 64 consecutive elements as one access: the C entry refuses (hipErrorNotSupported) pointers
+        # below that alignment -- a view at an odd storage offset -- and torch's ops take the call instead
+        al = cols // 64 * x.element_size()
+        fused = all(t is None or t.data_ptr() % al == 0 for t in (xc, rc, w, b, a2))
     if not fused:
         y = norm(x if residual is None else x + residual)
         return y if then_add is None else (y, y + then_add)
-    xc = x.contiguous()
-    rc = None if residual is None else residual.to(x.dtype).contiguous()
     out = torch.empty_like(xc)
-    cols = xc.shape[-1]
     rows = xc.numel() // cols
-    w = norm.weight.detach().contiguous() if norm.weight is not None else None
-    b = norm.bias.detach().contiguous() if norm.bias is not None else None
-    a2 = None if then_add is None else then_add.contiguous()
     out2 = None if then_add is None else torch.empty_like(xc)
     with torch.cuda.device(x.device):
         code = getattr(_lib.lib(), f"mvdetr_add_layernorm_add_{_lib.suffix(x.dtype, half_ok=True)}")(

@@ -331,3 +331,24 @@ def skew_reference(case):
             gv, gl, ga, loc = fused_reference(value, shapes, lsi, refp, raw, rows, go)
         _SKEW_REF[case] = dict(gv=gv.float(), gl=gl.float(), ga=ga.float(), shapes=shapes, rows=rows, smooth=texel_smooth(loc, shapes))
     return _SKEW_REF[case]
+
+
+# ---- the 16-bit bar: one rounding on the way out (test_half_inference_gpu.py, test_half_edges_gpu.py) ----
+def ulp_of(dtype):
+    return 2.0 ** -11 if dtype == torch.float16 else 2.0 ** -8
+
+
+def assert_rounded_once(out, ref, dtype, floor, extra=None):
+    """|out - ref| <= ulp |ref| + floor (+ extra) on EVERY element, and out is ref rounded to nearest on >= 99 % of them."""
+    assert out.dtype == dtype and out.shape == ref.shape
+    o = out.detach().cpu()
+    err = (o.double() - ref.double()).abs()
+    bar = ulp_of(dtype) * ref.double().abs() + floor
+    if extra is not None:
+        bar = bar + extra
+    worst = (err - bar).max().item()
+    same = (o == ref.to(dtype)).float().mean().item()
+    print(f"max |err| {err.max().item():.3e}, max (err - bar) {worst:.3e}, rounded-equal {same:.5f}")
+    assert (err <= bar).all(), (err.max().item(), worst)
+    assert same >= 0.99, same
+    return same

@@ -8,7 +8,7 @@ import pytest
 import torch
 from torch import nn
 
-from helpers import fused_plain, fused_train_inputs, smooth_features
+from helpers import assert_rounded_once, fused_plain, fused_train_inputs, smooth_features, ulp_of
 from oracle import c_oracle, torch_oracle
 
 pytestmark = pytest.mark.gpu
@@ -16,26 +16,6 @@ pytestmark = pytest.mark.gpu
 DTYPES = [torch.float16, torch.bfloat16]
 FP32_TOL = 1e-4                                           # tests/test_msda_gpu.py, tests/test_warp_gpu.py
 LN_FP32_TOL = 5e-6                                        # tests/test_layernorm_gpu.py
-
-
-def ulp_of(dtype):
-    return 2.0 ** -11 if dtype == torch.float16 else 2.0 ** -8
-
-
-def assert_rounded_once(out, ref, dtype, floor, extra=None):
-    """|out - ref| <= ulp |ref| + floor (+ extra) on EVERY element, and out is ref rounded to nearest on >= 99 % of them."""
-    assert out.dtype == dtype and out.shape == ref.shape
-    o = out.detach().cpu()
-    err = (o.double() - ref.double()).abs()
-    bar = ulp_of(dtype) * ref.double().abs() + floor
-    if extra is not None:
-        bar = bar + extra
-    worst = (err - bar).max().item()
-    same = (o == ref.to(dtype)).float().mean().item()
-    print(f"max |err| {err.max().item():.3e}, max (err - bar) {worst:.3e}, rounded-equal {same:.5f}")
-    assert (err <= bar).all(), (err.max().item(), worst)
-    assert same >= 0.99, same
-    return same
 
 
 # ---- warp ------------------------------------------------------------------------------------------------------------------
