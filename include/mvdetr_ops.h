@@ -650,6 +650,41 @@ int mvdetr_distance_nms_host_f32(const float *points, const float *scores, int n
 int mvdetr_distance_nms_host_f64(const double *points, const double *scores, int n, double dist_thres, int top_k, int64_t *keep,
                                  int32_t *count);
 
+/* Frame ingest: uint8 camera frames [k, src_h, src_w, 3] (pixels dense: 3 bytes each, src_w of them per row; frame_stride and
+ * row_stride in BYTES are free, so a cropped view is read in place) -> out [k, 3, dst_h, dst_w] in NCHW memory, or
+ * [k, dst_h, dst_w, 3] (channels-last) with layout_nhwc != 0.  One pass does the reference dataset's augmentation warp, ToTensor,
+ * Normalize and Resize:
+ *   out[k, c, y, x] = sum over the 4 taps of the bilinear resize (F.interpolate, align_corners=False, no antialias; positions
+ *   ((2x + 1) src_w - dst_w) / (2 dst_w), formed from integers, clamped below at 0, second tap min(x0 + 1, src_w - 1)) of
+ *   A[k, c, yy, xx] * a_c + b_c, with a_c = 1 / (255 std_c) and b_c = -mean_c / std_c supplied by the caller.
+ * A is the frame itself when mats is null.  Otherwise mats [k, 9] (row-major 3x3, fp64, destination pixel <- source pixel,
+ * integer pixel centres: cv2.warpPerspective's convention) and A[yy, xx] is the bilinear blend of the four frame pixels
+ * around (u / w, v / w), (u, v, w) = mats^-1 (xx, yy, 1) in fp64, every tap outside the frame = `border` (a grey level), and
+ * = border where w <= 0 or the position or the inverse is not finite.  A is not rounded to uint8.  The blend is fp32; the
+ * 16-bit outputs round once on the store.  Sizes up to 16384, k up to 65535.  No allocation, no synchronisation.
+ * mvdetr_ingest_last_kernel: the kernel the last call of this process launched ("ingest_identity_wide" -- aligned 16-byte
+ * loads, frames / strides multiples of 16; "ingest_identity_narrow"; "ingest_identity_direct" -- no LDS, large downscales;
+ * "ingest_warp"; "none"). */
+int mvdetr_ingest_frames_f32(void *stream, const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats,
+                             float a0, float a1, float a2, float b0, float b1, float b2, int k, int src_h, int src_w, int dst_h,
+                             int dst_w, int layout_nhwc, float border, float *out);
+int mvdetr_ingest_frames_f16(void *stream, const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats,
+                             float a0, float a1, float a2, float b0, float b1, float b2, int k, int src_h, int src_w, int dst_h,
+                             int dst_w, int layout_nhwc, float border, uint16_t *out);
+int mvdetr_ingest_frames_bf16(void *stream, const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats,
+                              float a0, float a1, float a2, float b0, float b1, float b2, int k, int src_h, int src_w, int dst_h,
+                              int dst_w, int layout_nhwc, float border, uint16_t *out);
+const char *mvdetr_ingest_last_kernel(void);
+
+/* frame ingest on host memory: the same contract without the stream, scale / bias / border as doubles (the f32 entry rounds
+ * them to float and blends in float, the f64 entry blends in double); threads own output rows */
+int mvdetr_ingest_frames_host_f32(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, double a0,
+                                  double a1, double a2, double b0, double b1, double b2, int k, int src_h, int src_w, int dst_h,
+                                  int dst_w, int layout_nhwc, double border, float *out);
+int mvdetr_ingest_frames_host_f64(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, double a0,
+                                  double a1, double a2, double b0, double b1, double b2, int k, int src_h, int src_w, int dst_h,
+                                  int dst_w, int layout_nhwc, double border, double *out);
+
 #ifdef __cplusplus
 }
 #endif

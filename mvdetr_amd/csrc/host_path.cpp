@@ -854,3 +854,125 @@ MVDETR_DETECT_HOST_ENTRIES(float, f32)
 MVDETR_DETECT_HOST_ENTRIES(double, f64)
 
 }  // extern "C"
+
+// ---- frame ingest ----------------------------------------------------------------------------------------------------------
+// uint8 frames -> normalised, resized (and optionally perspective-augmented) float images: the contract of mvdetr_ingest_frames_*
+// in include/mvdetr_ops.h.  Resize taps come from integers (floor and remainder of ((2i + 1) src - dst) / (2 dst)), the
+// augmentation's source positions from an fp64 inverse; the blend runs in T on grey levels and ends with one multiply-add.
+namespace {
+
+template <typename T> inline void resize_tap_host(int i, int src, int dst, int &i0, T &lam)
+{
+    const int64_t num = (int64_t)(2 * i + 1) * src - dst, den = 2 * (int64_t)dst;
+    if (num <= 0) {
+        i0 = 0;
+        lam = T(0);
+        return;
+    }
+    i0 = (int)(num / den);
+    lam = (T)(num - i0 * den) / (T)den;
+}
+
+template <typename T> inline T blend4_host(T p00, T p01, T p10, T p11, T wx, T wy)
+{
+    const T top = std::fma(wx, p01 - p00, p00), bot = std::fma(wx, p11 - p10, p10);
+    return std::fma(wy, bot - top, top);
+}
+
+template <typename T>
+inline void augmented_pixel_host(const uint8_t *frame, int64_t row_stride, int Hs, int Ws, const double *inv, bool inv_ok, T border, int xx,
+                                 int yy, T *A)
+{
+    A[0] = A[1] = A[2] = border;
+    const double u = inv[0] * xx + inv[1] * yy + inv[2], t = inv[3] * xx + inv[4] * yy + inv[5], w = inv[6] * xx + inv[7] * yy + inv[8];
+    if (!inv_ok || !(w > 0.0)) return;
+    const double px = u / w, py = t / w;
+    if (!(px > -1.0 && px < (double)Ws && py > -1.0 && py < (double)Hs)) return;
+    const double fx = std::floor(px), fy = std::floor(py);
+    const T lx = (T)(px - fx), ly = (T)(py - fy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const bool vx0 = x0 >= 0, vx1 = x0 + 1 < Ws, vy0 = y0 >= 0, vy1 = y0 + 1 < Hs;
+    const uint8_t *r0 = frame + (int64_t)std::max(y0, 0) * row_stride, *r1 = frame + (int64_t)std::min(y0 + 1, Hs - 1) * row_stride;
+    const int c0 = std::max(x0, 0) * 3, c1 = std::min(x0 + 1, Ws - 1) * 3;
+    for (int c = 0; c < 3; ++c)
+        A[c] = blend4_host<T>(vy0 && vx0 ? (T)r0[c0 + c] : border, vy0 && vx1 ? (T)r0[c1 + c] : border,
+                              vy1 && vx0 ? (T)r1[c0 + c] : border, vy1 && vx1 ? (T)r1[c1 + c] : border, lx, ly);
+}
+
+template <typename T>
+int ingest_host(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, const double *a_in, const double *b_in,
+                int K, int Hs, int Ws, int Ho, int Wo, int nhwc, double border_in, T *out)
+{
+    if (K < 0 || Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1 || Hs > 16384 || Ws > 16384 || Ho > 16384 || Wo > 16384 || K > 65535 ||
+        row_stride < (int64_t)Ws * 3 || frame_stride < 0 || (K > 0 && (!frames || !out)))
+        return 1;
+    const T a[3] = {(T)a_in[0], (T)a_in[1], (T)a_in[2]}, b[3] = {(T)b_in[0], (T)b_in[1], (T)b_in[2]}, border = (T)border_in;
+    std::vector<double> inv((size_t)K * 9, 0.0);
+    std::vector<char> good(K, 0);
+    if (mats)
+        for (int k = 0; k < K; ++k) {
+            good[k] = invert3(mats + (size_t)k * 9, &inv[(size_t)k * 9]);
+            for (int i = 0; i < 9; ++i) good[k] = good[k] && std::isfinite(inv[(size_t)k * 9 + i]);
+        }
+    const double *invp = inv.data();
+    const char *goodp = good.data();
+    parallel_ranges((int64_t)K * Ho, [=](int64_t first, int64_t last) {
+        for (int64_t u = first; u < last; ++u) {
+            const int k = (int)(u / Ho), y = (int)(u % Ho);
+            const uint8_t *frame = frames + (int64_t)k * frame_stride;
+            int y0;
+            T wy;
+            resize_tap_host<T>(y, Hs, Ho, y0, wy);
+            const int y1 = std::min(y0 + 1, Hs - 1);
+            for (int x = 0; x < Wo; ++x) {
+                int x0;
+                T wx;
+                resize_tap_host<T>(x, Ws, Wo, x0, wx);
+                const int x1 = std::min(x0 + 1, Ws - 1);
+                T A[4][3];
+                if (mats) {
+                    const double *iv = invp + (size_t)k * 9;
+                    augmented_pixel_host<T>(frame, row_stride, Hs, Ws, iv, goodp[k], border, x0, y0, A[0]);
+                    augmented_pixel_host<T>(frame, row_stride, Hs, Ws, iv, goodp[k], border, x1, y0, A[1]);
+                    augmented_pixel_host<T>(frame, row_stride, Hs, Ws, iv, goodp[k], border, x0, y1, A[2]);
+                    augmented_pixel_host<T>(frame, row_stride, Hs, Ws, iv, goodp[k], border, x1, y1, A[3]);
+                } else {
+                    const uint8_t *r0 = frame + (int64_t)y0 * row_stride, *r1 = frame + (int64_t)y1 * row_stride;
+                    for (int c = 0; c < 3; ++c) {
+                        A[0][c] = (T)r0[x0 * 3 + c];
+                        A[1][c] = (T)r0[x1 * 3 + c];
+                        A[2][c] = (T)r1[x0 * 3 + c];
+                        A[3][c] = (T)r1[x1 * 3 + c];
+                    }
+                }
+                for (int c = 0; c < 3; ++c) {
+                    const T v = std::fma(blend4_host<T>(A[0][c], A[1][c], A[2][c], A[3][c], wx, wy), a[c], b[c]);
+                    const int64_t at = nhwc ? (((int64_t)k * Ho + y) * Wo + x) * 3 + c : (((int64_t)k * 3 + c) * Ho + y) * Wo + x;
+                    out[at] = v;
+                }
+            }
+        }
+    });
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdetr_ingest_frames_host_f32(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, double a0,
+                                  double a1, double a2, double b0, double b1, double b2, int k, int src_h, int src_w, int dst_h,
+                                  int dst_w, int layout_nhwc, double border, float *out)
+{
+    const double a[3] = {a0, a1, a2}, b[3] = {b0, b1, b2};
+    return ingest_host<float>(frames, frame_stride, row_stride, mats, a, b, k, src_h, src_w, dst_h, dst_w, layout_nhwc, border, out);
+}
+int mvdetr_ingest_frames_host_f64(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, double a0,
+                                  double a1, double a2, double b0, double b1, double b2, int k, int src_h, int src_w, int dst_h,
+                                  int dst_w, int layout_nhwc, double border, double *out)
+{
+    const double a[3] = {a0, a1, a2}, b[3] = {b0, b1, b2};
+    return ingest_host<double>(frames, frame_stride, row_stride, mats, a, b, k, src_h, src_w, dst_h, dst_w, layout_nhwc, border, out);
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@ from torch import nn
 from . import geometry
 from .ops import warp_perspective
 from .ops.detect import bev_detect
+from .ops.ingest import ingest_frames
 from .ops.trunk_epilogue import bn_act, bn_relu_maxpool, fused_bn_act_available, fused_bn_relu_maxpool_available
 from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat, TransformerWorldFeat
 
@@ -310,6 +311,27 @@ class MVDeTr(nn.Module):
                 self.world_feat._buffers[name] = self.world_feat._buffers[name].to(dtype)
         self.compute_dtype = dtype
         return self
+
+    def ingest(self, frames, M=None):
+        """Decoded camera frames, uint8 ``[B, N, Hs, Ws, 3]`` (or ``[N, Hs, Ws, 3]``: one frame), -> the ``imgs`` that ``forward``,
+        ``detect`` and the training step take, ``[B, N, 3, H, W]`` at the geometry's ``input_img_shape``: the dataset's ToTensor,
+        Normalize and Resize (frameDataset.py:66-67,199-206) -- and, with ``M [B, N, 3, 3]``, its augmentation warp of the image
+        (image_utils.py:43; the SAME ``M`` then goes to ``forward``) -- as one HIP pass (ops/ingest.py).  The result has the model's
+        compute dtype and, with ``channels_last``, is a view of a ``[B N, 3, H, W]`` channels-last tensor: ``features`` then copies
+        nothing."""
+        if frames.dim() == 4:
+            frames = frames.unsqueeze(0)
+        return ingest_frames(frames, M, out_hw=self.geom.input_img_shape, dtype=self.compute_dtype or torch.float32,
+                             channels_last=self.channels_last)
+
+    def detect_frames(self, frames, M=None, **detect_kw):
+        """``detect(self.ingest(frames, M), M, **detect_kw)``; without ``M`` the frames are not augmented (identity matrices)."""
+        if frames.dim() == 4:
+            frames = frames.unsqueeze(0)
+        imgs = self.ingest(frames, M)
+        if M is None:
+            M = torch.eye(3).repeat(frames.shape[0], frames.shape[1], 1, 1)
+        return self.detect(imgs, M, **detect_kw)
 
     def features(self, imgs):
         B, N, C, H, W = imgs.shape

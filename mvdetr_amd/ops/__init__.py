@@ -17,3 +17,4 @@ from .trunk_epilogue import bn_act, bn_relu_maxpool, set_trunk_fusion  # noqa: E
 from .deform_conv import deform_conv2d, DeformConv2d, DeformConv2dFunction  # noqa: E402,F401
 from .attention import attention, MultiheadAttention, AttentionFunction  # noqa: E402,F401
 from .detect import bev_detect, distance_nms, Detections  # noqa: E402,F401
+from .ingest import ingest_frames  # noqa: E402,F401
