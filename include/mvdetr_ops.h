@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route */
+#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16 (purely additive again) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -333,9 +333,28 @@ int mvdetr_bn_act_f32(void *stream, const float *x, const float *mean, const flo
  * it (64, 128, ..., 1024, 2048, ...): hipErrorNotSupported (801) otherwise. */
 int mvdetr_bn_relu_maxpool_f32(void *stream, const float *x, const float *mean, const float *var, const float *gamma,
                                const float *beta, float eps, int n, int h, int w, int channels, float *y);
+/* The same two passes over 16-bit activations (float16 / bfloat16 as raw uint16_t words, channel-last): x, res and y
+ * are 16-bit, the BatchNorm vectors stay fp32 (MVDeTr.to_inference keeps them so).  Every step is fp32 -- the sum
+ * bn(x) + identity is not rounded in between, the pool takes its max on fp32 values -- and the result is rounded once,
+ * to nearest-even, on the way out.  A lane owns eight channels (one 16-byte access): channels must be a multiple of 8
+ * (hipErrorInvalidValue otherwise), and the pool wants channels/8 to divide 256 or be a multiple of it
+ * (hipErrorNotSupported otherwise).  Everything else -- arguments, aliasing (y may be x, res never y), validation --
+ * as the _f32 entries above. */
+int mvdetr_bn_act_f16(void *stream, const uint16_t *x, const float *mean, const float *var, const float *gamma,
+                      const float *beta, float eps, const uint16_t *res, const float *res_mean, const float *res_var,
+                      const float *res_gamma, const float *res_beta, float res_eps, int64_t rows, int channels, int relu,
+                      uint16_t *y);
+int mvdetr_bn_act_bf16(void *stream, const uint16_t *x, const float *mean, const float *var, const float *gamma,
+                       const float *beta, float eps, const uint16_t *res, const float *res_mean, const float *res_var,
+                       const float *res_gamma, const float *res_beta, float res_eps, int64_t rows, int channels, int relu,
+                       uint16_t *y);
+int mvdetr_bn_relu_maxpool_f16(void *stream, const uint16_t *x, const float *mean, const float *var, const float *gamma,
+                               const float *beta, float eps, int n, int h, int w, int channels, uint16_t *y);
+int mvdetr_bn_relu_maxpool_bf16(void *stream, const uint16_t *x, const float *mean, const float *var, const float *gamma,
+                                const float *beta, float eps, int n, int h, int w, int channels, uint16_t *y);
 /* Name of the kernel the last trunk-epilogue call of this process launched ("bn_relu", "bn_add_relu", "bn_bn_add_relu",
- * "bn_relu_maxpool", ...; "none" before the first), and how many such launches there have been: tests tell the fused
- * path from torch's ops by them.  Static storage; never NULL. */
+ * "bn_relu_maxpool", ...; the 16-bit entries: the same names with "_half" appended; "none" before the first), and how
+ * many such launches there have been: tests tell the fused path from torch's ops by them.  Static storage; never NULL. */
 const char *mvdetr_trunk_last_kernel(void);
 int64_t mvdetr_trunk_launch_count(void);
 

@@ -91,6 +91,10 @@ SIGNATURES = {
     "mvdetr_add_layernorm_add_bf16": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
     "mvdetr_bn_act_f32": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),
     "mvdetr_bn_relu_maxpool_f32": ([_vp] * 6 + [ctypes.c_float] + [_i] * 4 + [_vp], _i),
+    "mvdetr_bn_act_f16": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),
+    "mvdetr_bn_act_bf16": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),
+    "mvdetr_bn_relu_maxpool_f16": ([_vp] * 6 + [ctypes.c_float] + [_i] * 4 + [_vp], _i),
+    "mvdetr_bn_relu_maxpool_bf16": ([_vp] * 6 + [ctypes.c_float] + [_i] * 4 + [_vp], _i),
     "mvdetr_trunk_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_trunk_launch_count": ([], ctypes.c_int64),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),

@@ -20,14 +20,28 @@ from . import geometry
 from .ops import warp_perspective
 from .ops.detect import bev_detect
 from .ops.ingest import ingest_frames
-from .ops.trunk_epilogue import bn_act, bn_relu_maxpool, fused_bn_act_available, fused_bn_relu_maxpool_available
+from .ops.trunk_epilogue import (bn_act, bn_act_half, bn_relu_maxpool, bn_relu_maxpool_half, fused_bn_act_available,
+                                  fused_bn_act_half_available, fused_bn_relu_maxpool_available,
+                                  fused_bn_relu_maxpool_half_available)
 from .world_feat import ConvWorldFeat, DeformConvWorldFeat, DeformTransWorldFeat, TransformerWorldFeat
+
+
+def _fused_bn_act(out, bn, residual=None, residual_bn=None):
+    """The fused pass that takes these arguments -- bn_act for fp32 activations, bn_act_half for 16-bit ones (asked in
+    that order) -- or None."""
+    if fused_bn_act_available(out, bn, residual, residual_bn):
+        return bn_act
+    if fused_bn_act_half_available(out, bn, residual, residual_bn):
+        return bn_act_half
+    return None
 
 
 def _bn_relu(out, bn, relu):
     """relu(bn(out)) for a convolution's fresh output: one in-place HIP pass in inference, torch's ops otherwise."""
-    if type(relu) is nn.ReLU and fused_bn_act_available(out, bn):
-        return bn_act(out, bn, relu=True, inplace=True)
+    if type(relu) is nn.ReLU:
+        op = _fused_bn_act(out, bn)
+        if op is not None:
+            return op(out, bn, relu=True, inplace=True)
     return relu(bn(out))
 
 
@@ -38,13 +52,15 @@ def _bn_add_relu(out, bn, x, downsample, relu):
     through its BatchNorm in the same pass; x itself is never written.  torch's ops otherwise, as in the reference."""
     if type(relu) is nn.ReLU:
         if downsample is None:
-            if fused_bn_act_available(out, bn, x):
-                return bn_act(out, bn, x, relu=True, inplace=True)
+            op = _fused_bn_act(out, bn, x)
+            if op is not None:
+                return op(out, bn, x, relu=True, inplace=True)
         elif type(downsample) is nn.Sequential and len(downsample) == 2 and type(downsample[0]) is nn.Conv2d \
-                and fused_bn_act_available(out, bn):
+                and _fused_bn_act(out, bn) is not None:
             raw = downsample[0](x)
-            if fused_bn_act_available(out, bn, raw, downsample[1]):
-                return bn_act(out, bn, raw, downsample[1], relu=True, inplace=True)
+            op = _fused_bn_act(out, bn, raw, downsample[1])
+            if op is not None:
+                return op(out, bn, raw, downsample[1], relu=True, inplace=True)
             return relu(bn(out) + downsample[1](raw))
     identity = x if downsample is None else downsample(x)
     return relu(bn(out) + identity)
@@ -61,6 +77,9 @@ class ResNetTrunk(nn.Sequential):
             x = mods[0](x)
             if fused_bn_relu_maxpool_available(x, mods[1], mods[2], mods[3]):
                 x = bn_relu_maxpool(x, mods[1])
+                mods = mods[4:]
+            elif fused_bn_relu_maxpool_half_available(x, mods[1], mods[2], mods[3]):
+                x = bn_relu_maxpool_half(x, mods[1])
                 mods = mods[4:]
             else:
                 mods = mods[1:]
@@ -288,7 +307,8 @@ class MVDeTr(nn.Module):
 
         The warp (fp32 matrices, fp64 source positions), the fused deformable attention (fp32 reference points, softmax and
         locations) and the add + LayerNorm tails (fp32 statistics) run their 16-bit-storage HIP kernels, each rounding once
-        on the way out; the trunk's BatchNorm / ReLU / max-pool run as torch's ops (their fused epilogues are float32).
+        on the way out; so do the trunk's BatchNorm / ReLU / residual-add / max-pool epilogues (ops/trunk_epilogue.py:
+        16-bit activations, the float32 BatchNorm vectors kept above; ``bn(x) + identity`` is not rounded in between).
         ``forward`` then returns 16-bit head maps; ``detect`` upcasts the two world maps for the detection extraction.
         Served for the ``deform_trans`` and ``conv`` world features; training, ``torch.autocast`` and the backward are not
         part of it."""

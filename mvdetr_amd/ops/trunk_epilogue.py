@@ -1,7 +1,10 @@
 """The ResNet trunk's inference epilogues in one HIP pass each (csrc/trunk_epilogue.hip): eval-mode BatchNorm2d fused
 with the ReLU / residual add / downsample BatchNorm that follows it in a residual block, and the stem's
-BatchNorm + ReLU + MaxPool2d(3, 2, 1).  Channel-last fp32 CUDA tensors only; everything else -- training, autograd,
-other dtypes and layouts, the CPU -- runs the modules' own torch ops (the callers in model.py ask the predicates first)."""
+BatchNorm + ReLU + MaxPool2d(3, 2, 1).  Channel-last fp32 CUDA tensors (bn_act, bn_relu_maxpool) or channel-last
+float16 / bfloat16 ones with the BatchNorm's vectors in fp32, as MVDeTr.to_inference leaves them (bn_act_half,
+bn_relu_maxpool_half: fp32 arithmetic on 16-bit storage, one rounding on the way out); everything else -- training,
+autograd, other dtypes and layouts, the CPU -- runs the modules' own torch ops (the callers in model.py ask the
+predicates first)."""
 from __future__ import annotations
 
 import os
@@ -36,9 +39,12 @@ def launch_count() -> int:
     return int(_lib.lib().mvdetr_trunk_launch_count())
 
 
-def _activation_ok(x) -> bool:
-    # channel-last memory, dense: the kernels index it as [N*H*W, C]
-    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0
+HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _activation_ok(x, dtypes=(torch.float32,), vec=4) -> bool:
+    # channel-last memory, dense: the kernels index it as [N*H*W, C]; a lane owns `vec` channels (16 bytes)
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in dtypes and x.dim() == 4 and x.shape[1] % vec == 0
             and x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0)
 
 
@@ -63,20 +69,32 @@ def _bn_ok(bn, x) -> bool:
     return not (torch.is_grad_enabled() and (x.requires_grad or any(v.requires_grad for v in vecs)))
 
 
-def fused_bn_act_available(x: torch.Tensor, bn: nn.Module, residual: torch.Tensor = None, residual_bn: nn.Module = None) -> bool:
-    """True when bn_act() runs the HIP kernel for these arguments: the switch is on, CUDA fp32 channel-last activations
-    with C % 4 == 0, BatchNorm2d modules in eval mode with running statistics, a residual of the same shape and
-    layout, and nothing that needs autograd."""
-    if not (_enabled and _activation_ok(x) and _bn_ok(bn, x)):
+def _bn_act_ok(x, bn, residual, residual_bn, dtypes, vec) -> bool:
+    if not (_enabled and _activation_ok(x, dtypes, vec) and _bn_ok(bn, x)):
         return False
     if residual is None:
         return residual_bn is None
-    if not (_activation_ok(residual) and residual.shape == x.shape and residual.device == x.device
+    if not (_activation_ok(residual, (x.dtype,), vec) and residual.shape == x.shape and residual.device == x.device
             and not _overlap(residual, x)):
         return False
     if torch.is_grad_enabled() and residual.requires_grad:
         return False
     return residual_bn is None or _bn_ok(residual_bn, residual)
+
+
+def fused_bn_act_available(x: torch.Tensor, bn: nn.Module, residual: torch.Tensor = None, residual_bn: nn.Module = None) -> bool:
+    """True when bn_act() runs the HIP kernel for these arguments: the switch is on, CUDA fp32 channel-last activations
+    with C % 4 == 0, BatchNorm2d modules in eval mode with running statistics, a residual of the same shape and
+    layout, and nothing that needs autograd."""
+    return _bn_act_ok(x, bn, residual, residual_bn, (torch.float32,), 4)
+
+
+def fused_bn_act_half_available(x: torch.Tensor, bn: nn.Module, residual: torch.Tensor = None,
+                                residual_bn: nn.Module = None) -> bool:
+    """True when bn_act_half() runs the 16-bit HIP kernel: as fused_bn_act_available(), but x is float16 or bfloat16,
+    the residual has x's dtype, C % 8 == 0, and the BatchNorm's vectors are fp32 (a BatchNorm cast to 16 bits, as by
+    ``model.half()``, is refused and keeps torch's ops)."""
+    return _bn_act_ok(x, bn, residual, residual_bn, HALF_DTYPES, 8)
 
 
 def _bn_args(bn):
@@ -86,6 +104,21 @@ def _bn_args(bn):
             0 if bn.bias is None else bn.bias.data_ptr(), float(bn.eps))
 
 
+def _suffix(dtype) -> str:
+    return {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[dtype]
+
+
+def _run_bn_act(x, bn, residual, residual_bn, relu, inplace):
+    y = x if inplace else torch.empty_like(x)
+    C = x.shape[1]
+    with torch.cuda.device(x.device):
+        code = getattr(_lib.lib(), "mvdetr_bn_act_" + _suffix(x.dtype))(
+            _lib.current_stream_ptr(x.device), x.data_ptr(), *_bn_args(bn), 0 if residual is None else residual.data_ptr(),
+            *_bn_args(residual_bn), x.numel() // C, C, int(bool(relu)), y.data_ptr())
+    _lib.check(code, "bn_act")
+    return y
+
+
 def bn_act(x: torch.Tensor, bn: nn.BatchNorm2d, residual: torch.Tensor = None, residual_bn: nn.BatchNorm2d = None,
            relu: bool = True, inplace: bool = False) -> torch.Tensor:
     """``act(bn(x) [+ residual | + residual_bn(residual)])`` in one pass; ``inplace`` overwrites x (pass only a tensor
@@ -93,42 +126,68 @@ def bn_act(x: torch.Tensor, bn: nn.BatchNorm2d, residual: torch.Tensor = None, r
     fused_bn_act_available() is False: callers decide, nothing falls back silently here."""
     if not fused_bn_act_available(x, bn, residual, residual_bn):
         raise RuntimeError("bn_act: these arguments do not take the fused kernel (see fused_bn_act_available)")
-    y = x if inplace else torch.empty_like(x)
-    C = x.shape[1]
-    with torch.cuda.device(x.device):
-        code = _lib.lib().mvdetr_bn_act_f32(
-            _lib.current_stream_ptr(x.device), x.data_ptr(), *_bn_args(bn), 0 if residual is None else residual.data_ptr(),
-            *_bn_args(residual_bn), x.numel() // C, C, int(bool(relu)), y.data_ptr())
-    _lib.check(code, "bn_act")
-    return y
+    return _run_bn_act(x, bn, residual, residual_bn, relu, inplace)
 
 
-def fused_bn_relu_maxpool_available(x: torch.Tensor, bn: nn.Module, relu: nn.Module, pool: nn.Module) -> bool:
-    """True when bn_relu_maxpool() runs the HIP kernel: as fused_bn_act_available(), a plain ReLU, and the pool exactly
-    MaxPool2d(kernel 3, stride 2, padding 1, dilation 1, ceil_mode False) without indices."""
+def bn_act_half(x: torch.Tensor, bn: nn.BatchNorm2d, residual: torch.Tensor = None, residual_bn: nn.BatchNorm2d = None,
+                relu: bool = True, inplace: bool = False) -> torch.Tensor:
+    """bn_act() over float16 / bfloat16 activations with fp32 BatchNorm vectors: every step in fp32 -- the sum
+    ``bn(x) + residual`` is not rounded in between, where torch's 16-bit chain rounds after each op -- and one rounding
+    to nearest-even at the store.  Raises when fused_bn_act_half_available() is False."""
+    if not fused_bn_act_half_available(x, bn, residual, residual_bn):
+        raise RuntimeError("bn_act_half: these arguments do not take the fused kernel (see fused_bn_act_half_available)")
+    return _run_bn_act(x, bn, residual, residual_bn, relu, inplace)
+
+
+def _pool_ok(x, bn, relu, pool, dtypes, vec) -> bool:
     def two(v, want):
         return v == want or v == (want, want)
-    if not (_enabled and _activation_ok(x) and _bn_ok(bn, x) and type(relu) is nn.ReLU and type(pool) is nn.MaxPool2d):
+    if not (_enabled and _activation_ok(x, dtypes, vec) and _bn_ok(bn, x) and type(relu) is nn.ReLU and type(pool) is nn.MaxPool2d):
         return False
-    cg = x.shape[1] // 4
+    cg = x.shape[1] // vec
     if not (256 % cg == 0 if cg <= 256 else cg % 256 == 0):
         return False
     return (two(pool.kernel_size, 3) and two(pool.stride, 2) and two(pool.padding, 1) and two(pool.dilation, 1)
             and not pool.ceil_mode and not pool.return_indices)
 
 
-def bn_relu_maxpool(x: torch.Tensor, bn: nn.BatchNorm2d) -> torch.Tensor:
-    """``max_pool2d(relu(bn(x)), 3, 2, 1)`` in one pass over x (channel-last in, channel-last out)."""
-    if not fused_bn_relu_maxpool_available(x, bn, _RELU, _POOL):
-        raise RuntimeError("bn_relu_maxpool: these arguments do not take the fused kernel (see fused_bn_relu_maxpool_available)")
+def fused_bn_relu_maxpool_available(x: torch.Tensor, bn: nn.Module, relu: nn.Module, pool: nn.Module) -> bool:
+    """True when bn_relu_maxpool() runs the HIP kernel: as fused_bn_act_available(), a plain ReLU, and the pool exactly
+    MaxPool2d(kernel 3, stride 2, padding 1, dilation 1, ceil_mode False) without indices."""
+    return _pool_ok(x, bn, relu, pool, (torch.float32,), 4)
+
+
+def fused_bn_relu_maxpool_half_available(x: torch.Tensor, bn: nn.Module, relu: nn.Module, pool: nn.Module) -> bool:
+    """True when bn_relu_maxpool_half() runs the 16-bit HIP kernel: as fused_bn_act_half_available() and the same ReLU
+    and pool as fused_bn_relu_maxpool_available(); C / 8 must divide 256 or be a multiple of it."""
+    return _pool_ok(x, bn, relu, pool, HALF_DTYPES, 8)
+
+
+def _run_pool(x, bn):
     N, C, H, W = x.shape
     y = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
                     memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        code = _lib.lib().mvdetr_bn_relu_maxpool_f32(_lib.current_stream_ptr(x.device), x.data_ptr(), *_bn_args(bn), N, H, W, C,
-                                                     y.data_ptr())
+        code = getattr(_lib.lib(), "mvdetr_bn_relu_maxpool_" + _suffix(x.dtype))(
+            _lib.current_stream_ptr(x.device), x.data_ptr(), *_bn_args(bn), N, H, W, C, y.data_ptr())
     _lib.check(code, "bn_relu_maxpool")
     return y
+
+
+def bn_relu_maxpool(x: torch.Tensor, bn: nn.BatchNorm2d) -> torch.Tensor:
+    """``max_pool2d(relu(bn(x)), 3, 2, 1)`` in one pass over x (channel-last in, channel-last out)."""
+    if not fused_bn_relu_maxpool_available(x, bn, _RELU, _POOL):
+        raise RuntimeError("bn_relu_maxpool: these arguments do not take the fused kernel (see fused_bn_relu_maxpool_available)")
+    return _run_pool(x, bn)
+
+
+def bn_relu_maxpool_half(x: torch.Tensor, bn: nn.BatchNorm2d) -> torch.Tensor:
+    """bn_relu_maxpool() over float16 / bfloat16 activations with fp32 BatchNorm vectors: the max is taken on the fp32
+    values and rounded once, which equals ``max_pool2d(bn_act_half(x, bn), 3, 2, 1)`` bit for bit (rounding is monotone)."""
+    if not fused_bn_relu_maxpool_half_available(x, bn, _RELU, _POOL):
+        raise RuntimeError("bn_relu_maxpool_half: these arguments do not take the fused kernel "
+                           "(see fused_bn_relu_maxpool_half_available)")
+    return _run_pool(x, bn)
 
 
 _RELU, _POOL = nn.ReLU(), nn.MaxPool2d(3, 2, 1)

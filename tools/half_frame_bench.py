@@ -8,7 +8,15 @@ repetition by repetition (same call, alternating, spread first):
                   (msda_fwd_group2 / msda_fwd_fused_half);
   add_layernorm   ops.add_layer_norm alone with the second output, 75,600 rows x 128;
 
-each for float32, bfloat16 and float16.
+each for float32, bfloat16 and float16; then, for each 16-bit variant,
+
+  trunk           the whole 16-bit frame (MVDeTr.detect) with the trunk's fused epilogues on and off (ops.set_trunk_fusion),
+                  alternated the same way; the baseline of this row is the variant with torch's ops;
+  trunk_kernels   the four 16-bit epilogue kernels alone over the launches of one frame (bn_relu_half 8 launches,
+                  bn_add_relu_half 5, bn_bn_add_relu_half 3, bn_relu_maxpool_half 1, every launch on tensors of its own):
+                  bytes the pass must move (from the shapes) / device-event time.
+
+`--only a,b` runs just those rows.
 
     python tools/half_frame_bench.py [--reps N] [--config wildtrack]
 
@@ -33,6 +41,7 @@ from mvdetr_amd.model import build_model  # noqa: E402
 from mvdetr_amd.ops import MultiScaleDeformableAttention as MSDA  # noqa: E402
 from mvdetr_amd.ops import add_layer_norm, warp_perspective  # noqa: E402
 from mvdetr_amd.ops import warp as warp_mod  # noqa: E402
+from mvdetr_amd.ops import trunk_epilogue as te  # noqa: E402
 
 DEV = "cuda:0"
 VARIANTS = {"float32": None, "bfloat16": torch.bfloat16, "float16": torch.float16}
@@ -79,11 +88,55 @@ def detection_cells(model, imgs, M, thres):
     return set(det.cell[0, :min(n, det.cell.shape[1])].tolist())
 
 
+ROWS = ("detect", "hot_path", "warp", "msda", "add_layernorm", "trunk", "trunk_kernels", "detections")
+
+
+def trunk_kernel_launches(views, feat_hw, dtype, device):
+    """The fused 16-bit launches of one ResNet-18 frame, by kernel: name -> (closures, bytes the passes must move).  The
+    stem's convolution output is 4 x 4 the feature map (stride 2 of the stride-8 trunk), layer1 runs at 2 x 2 of it, layers
+    2 - 4 (dilated) at the feature map's size; 2 blocks per layer, a downsample branch in the first block of layers 2 - 4."""
+    from torch import nn
+    h, w = feat_hw
+
+    def act(c, hh, ww):
+        return torch.randn(views, c, hh, ww, device=device).to(dtype).contiguous(memory_format=torch.channels_last)
+
+    def bn(c):
+        # (mean 0, variance 1, gamma 1, beta 0: the passes run in place over and over, and their values must stay finite)
+        return nn.BatchNorm2d(c).to(device).eval().requires_grad_(False)
+
+    layers = [(64, 2 * h, 2 * w, False), (128, h, w, True), (256, h, w, True), (512, h, w, True)]
+    out = {"bn_relu_half": ([], 0), "bn_add_relu_half": ([], 0), "bn_bn_add_relu_half": ([], 0), "bn_relu_maxpool_half": ([], 0)}
+
+    def add(name, fn, nbytes):
+        fns, total = out[name]
+        out[name] = (fns + [fn], total + nbytes)
+
+    stem = act(64, 4 * h, 4 * w)
+    T = stem.numel() * stem.element_size()
+    add("bn_relu_maxpool_half", lambda x=stem, m=bn(64): te.bn_relu_maxpool_half(x, m), T + T // 4)
+    for c, hh, ww, down in layers:
+        for block in range(2):
+            x, m = act(c, hh, ww), bn(c)
+            T = x.numel() * x.element_size()
+            add("bn_relu_half", lambda x=x, m=m: te.bn_act_half(x, m, relu=True, inplace=True), 2 * T)
+            x, r, m = act(c, hh, ww), act(c, hh, ww), bn(c)
+            if down and block == 0:
+                add("bn_bn_add_relu_half", lambda x=x, r=r, m=m, m2=bn(c): te.bn_act_half(x, m, r, m2, relu=True, inplace=True), 3 * T)
+            else:
+                add("bn_add_relu_half", lambda x=x, r=r, m=m: te.bn_act_half(x, m, r, relu=True, inplace=True), 3 * T)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--config", default="wildtrack")
+    ap.add_argument("--only", default="", help="comma-separated rows to run (default: all): " + ", ".join(ROWS))
     a = ap.parse_args()
+    only = set(filter(None, a.only.split(","))) or set(ROWS)
+    if only - set(ROWS):
+        raise SystemExit(f"half_frame_bench: unknown rows {sorted(only - set(ROWS))}")
     if not torch.cuda.is_available():
         raise SystemExit("half_frame_bench: needs a GPU (no CPU fallback for timings)")
     from helpers import fused_train_inputs
@@ -97,7 +150,8 @@ def main():
         m = m.to(DEV).eval()
         models[name] = m if dtype is None else m.to_inference(dtype)
     ref_model = models["float32"]
-    N, (Hi, Wi), (H, W) = ref_model.num_cam, ref_model.geom.img_shape, ref_model.Rworld_shape
+    # (the frame the trunk sees: the dataset resizes the camera image to input_img_shape -- bench.py's frame)
+    N, (Hi, Wi), (H, W) = ref_model.num_cam, ref_model.geom.input_img_shape, ref_model.Rworld_shape
     imgs = torch.randn(1, N, 3, Hi, Wi, generator=torch.Generator().manual_seed(1000)).to(DEV)
     M = torch.eye(3).repeat(1, N, 1, 1)
 
@@ -139,6 +193,8 @@ def main():
 
         rows = []
         for what, variants in fns.items():
+            if what not in only:
+                continue
             res = {n: stats(t) for n, t in alternated(variants, a.reps).items()}
             base = res["float32"]
             spread = base["p90_us"] - base["p10_us"]
@@ -151,24 +207,73 @@ def main():
                 print(json.dumps(row), flush=True)
                 rows.append(row)
 
+        # the 16-bit frame with the trunk's fused epilogues on and off: the same model, the switch flipped inside the call
+        def frame(model, fused):
+            prev = te.set_trunk_fusion(fused)
+            try:
+                return model.detect(imgs, M)
+            finally:
+                te.set_trunk_fusion(prev)
+
+        for n in ("bfloat16", "float16") if "trunk" in only else ():
+            model = models[n]
+            before = te.launch_count()
+            frame(model, True)
+            launches, kernel = te.launch_count() - before, te.last_kernel()
+            frame(model, False)
+            assert te.launch_count() == before + launches
+            res = {k: stats(t) for k, t in alternated({"torch_ops": lambda model=model: frame(model, False),
+                                                       "fused": lambda model=model: frame(model, True)}, a.reps).items()}
+            base = res["torch_ops"]
+            spread = base["p90_us"] - base["p10_us"]
+            for k, r in res.items():
+                d = r["median_us"] - base["median_us"]
+                verdict = "baseline" if k == "torch_ops" else "faster" if -d > spread else "same" if d <= spread else "SLOWER"
+                row = {"what": "trunk", "variant": f"{n}/{k}", **{q: round(v, 1) for q, v in r.items()}, "fp32_spread_us": round(spread, 1),
+                       "ratio_to_fp32": round(r["median_us"] / base["median_us"], 3), "verdict": verdict,
+                       "kernel": f"{launches} fused launches, last {kernel}" if k == "fused" else "torch's BatchNorm / ReLU / add / max-pool"}
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+
+        # the four 16-bit epilogue kernels alone, over one frame's launches
+        kernel_rows = []
+        for n in ("bfloat16", "float16") if "trunk_kernels" in only else ():
+            h_feat, w_feat = models[n].features(imgs).shape[-2:]
+            for kernel, (launches, nbytes) in trunk_kernel_launches(N, (h_feat, w_feat), VARIANTS[n], DEV).items():
+                def once(launches=launches):
+                    for fn in launches:
+                        fn()
+                once()
+                assert te.last_kernel() == kernel, (te.last_kernel(), kernel)
+                r = stats(alternated({kernel: once}, a.reps)[kernel])
+                row = {"what": "trunk_kernels", "variant": n, "kernel": kernel, "launches": len(launches), "mbytes": round(nbytes / 1e6, 1),
+                       **{q: round(v, 1) for q, v in r.items()}, "tbytes_per_s": round(nbytes / r["median_us"] / 1e6, 2)}
+                print(json.dumps(row), flush=True)
+                kernel_rows.append(row)
+
         # detections on one seeded frame: the threshold at which float32 keeps its 300 best-scoring cells as candidates
         (hm, _), _ = ref_model(imgs, M)
         thres = float(torch.sigmoid(hm.float()).flatten().topk(300).values[-1])
-        cells = {n: detection_cells(m, imgs, M, thres) for n, m in models.items()}
-        for n in ("bfloat16", "float16"):
+        cells = {n: detection_cells(m, imgs, M, thres) for n, m in models.items()} if "detections" in only else {}
+        for n in ("bfloat16", "float16") if cells else ():
             row = {"what": "detections", "variant": n, "cls_thres": round(thres, 5), "kept_fp32": len(cells["float32"]),
                    "kept": len(cells[n]), "only_fp32": len(cells["float32"] - cells[n]), "only_16bit": len(cells[n] - cells["float32"])}
             print(json.dumps(row), flush=True)
             rows.append(row)
 
-    print(f"\n{'what':<14} {'variant':<9} {'median us':>10} {'p10':>10} {'p90':>10} {'min':>10} {'max':>10} {'fp32 spread':>12} {'/ fp32':>7}  verdict   kernel")
+    print(f"\n{'what':<14} {'variant':<19} {'median us':>10} {'p10':>10} {'p90':>10} {'min':>10} {'max':>10} {'fp32 spread':>12} {'/ fp32':>7}  verdict   kernel")
     for r in rows:
         if r["what"] == "detections":
-            print(f"{'detections':<14} {r['variant']:<9} kept by float32 {r['kept_fp32']}, by {r['variant']} {r['kept']}; only in float32 "
+            print(f"{'detections':<14} {r['variant']:<19} kept by float32 {r['kept_fp32']}, by {r['variant']} {r['kept']}; only in float32 "
                   f"{r['only_fp32']}, only in {r['variant']} {r['only_16bit']} (cls_thres {r['cls_thres']})")
             continue
-        print(f"{r['what']:<14} {r['variant']:<9} {r['median_us']:>10.1f} {r['p10_us']:>10.1f} {r['p90_us']:>10.1f} {r['min_us']:>10.1f} "
+        print(f"{r['what']:<14} {r['variant']:<19} {r['median_us']:>10.1f} {r['p10_us']:>10.1f} {r['p90_us']:>10.1f} {r['min_us']:>10.1f} "
               f"{r['max_us']:>10.1f} {r['fp32_spread_us']:>12.1f} {r['ratio_to_fp32']:>7.3f}  {r['verdict']:<9} {r['kernel']}")
+    if kernel_rows:
+        print(f"\n{'kernel (one frame of launches)':<32} {'variant':<9} {'launches':>8} {'MB':>9} {'median us':>10} {'p10':>9} {'p90':>9} {'TB/s':>6}")
+        for r in kernel_rows:
+            print(f"{r['kernel']:<32} {r['variant']:<9} {r['launches']:>8} {r['mbytes']:>9.1f} {r['median_us']:>10.1f} {r['p10_us']:>9.1f} "
+                  f"{r['p90_us']:>9.1f} {r['tbytes_per_s']:>6.2f}")
 
 
 if __name__ == "__main__":
