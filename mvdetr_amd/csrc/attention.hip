@@ -91,7 +91,10 @@ template <typename T> __device__ __forceinline__ T attn_dot(const T *__restrict_
 }
 
 // one wave per query row; pass 1: lse over the keys (each lane an online (max, sum) of its keys, merged by a fixed
-// butterfly); pass 2: 64 probabilities at a time through LDS, lanes own channels d = lane + 64 c
+// butterfly); pass 2: 64 probabilities at a time through LDS, lanes own channels d = lane + 64 c.  A probability is
+// exp(s - max) / sum, NOT exp(s - lse): lse is a rounded number of the logits' magnitude, and probabilities off by
+// eps |lse| each no longer sum to 1 -- at logits ~ 80 a saturated row's out, and through delta = grad_out . out the
+// backward's dS (a small difference there), would carry 1e-5 of their operands' size
 template <typename T, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_generic(const T *__restrict__ q, const T *__restrict__ k,
                                                         const T *__restrict__ v, T *__restrict__ out, T *__restrict__ lse,
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256) void attn_fwd_generic(const T *__restrict__ q,
             l = (m == -INFINITY ? T(0) : l * attn_exp(m - mm)) + (m2 == -INFINITY ? T(0) : l2 * attn_exp(m2 - mm));
             m = mm;
         }
-        const T L = m + attn_log(l);
+        const T L = m + attn_log(l), inv_l = T(1) / l;
         T acc[ATTN_GD / 64];
 #pragma unroll
         for (int c = 0; c < ATTN_GD / 64; ++c) acc[c] = T(0);
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(256) void attn_fwd_generic(const T *__restrict__ q,
             const int j = j0 + lane;
             T pv = T(0);
             if (j < p.Sk) {
-                pv = attn_exp(scale * attn_dot(sq[wave], kb + j * p.k[2], p.D) - L);
+                pv = attn_exp(scale * attn_dot(sq[wave], kb + j * p.k[2], p.D) - m) * inv_l;
                 if (DROP) pv = attn_keep(p, b, hd, i, j) ? pv * T(p.inv_keep) : T(0);
             }
             __syncthreads();

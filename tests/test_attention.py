@@ -6,7 +6,12 @@ from |.|-operand quantities (score error (D + 4) eps A_ij + 4 eps max_j A_ij wit
 the probabilities as a relative error; a random-walk accumulation term 2 (sqrt(Sk) + 4) eps sum_j p_ij |v_jd|), times
 MARGIN = 1, the smallest whole number with which torch's own fp32 composition passes at every size and seed used here and in
 test_attention_gpu.py (observed err / bar: torch's composition <= 0.07, the host path <= 0.10, the device kernels <= 0.08).  The bar
-tests itself: the oracle with one key left out must exceed it, torch's fp32 composition must pass it."""
+tests itself: the oracle with one key left out must exceed it, torch's fp32 composition must pass it.
+
+Gradients are held to attention_oracle.grad_bars_elementwise (one bound per gradient element, formula in that module's
+docstring) on the case table of attention_cases.py: the bars test themselves against torch's fp32 composition (MARGIN = 1) and
+nine oracle-made mutants, and the host path runs every case of the table in fp32 and fp64, strided layouts bit-equal to the
+dense run.  test_attention_gpu.py runs the same table on the device."""
 import math
 
 import numpy as np
@@ -14,6 +19,7 @@ import pytest
 import torch
 from torch import nn
 
+import attention_cases as ac
 import attention_oracle as ao
 from conftest import load_golden, t
 
@@ -124,6 +130,111 @@ def test_host_path_fp64_gradcheck():
     v = torch.randn(1, 2, 7, 3, generator=g, dtype=torch.float64).requires_grad_(True)
     assert torch.autograd.gradcheck(op.attention, (q, k, v), eps=1e-6, atol=1e-7)
     assert torch.autograd.gradcheck(lambda a, b, c: op.attention(a, b, c, 0.3, 9), (q, k, v), eps=1e-6, atol=1e-7)
+
+
+# ---- the case table (attention_cases.py): bars, mutants, the host path ------------------------------------------------------
+
+def _composition_with_grads(case, seed):
+    """torch's own fp32 composition differentiated by autograd, with the case's keep mask: the reference MARGIN is set by."""
+    q, k, v, gout = ac.make_inputs(case, seed)
+    leaves = [x.clone().requires_grad_(True) for x in (q, k, v)]
+    P = torch.softmax(leaves[0] @ leaves[1].transpose(-1, -2) * (1.0 / math.sqrt(case.D)), -1)
+    if case.dropout:
+        P = P * ac.keep_mask(case) / (1.0 - case.dropout)
+    (P @ leaves[2]).backward(gout)
+    return [x.grad for x in leaves]
+
+
+@pytest.mark.parametrize("name", ["m16_33x97_seq", "m32_129x1", "w65_5x70_drop", "m32_65x130_amp80"])
+def test_explicit_gradient_formulas_are_autograds(name):
+    """The formulas the mutants are altered copies of give autograd's gradients when nothing is altered."""
+    case = ac.by_name(name)
+    q, k, v, gout = ac.make_inputs(case)
+    for a, b in zip(ao.grads_explicit(q, k, v, gout, ac.keep_mask(case), case.dropout), ac.oracle(case).grads):
+        assert torch.allclose(a, b, atol=1e-12 * max(1.0, b.abs().max().item()), rtol=1e-10)
+
+
+@pytest.mark.parametrize("case", ac.TABLE, ids=lambda c: c.name)
+def test_the_gradient_bars_test_themselves(case):
+    """At every case and seed: torch's fp32 composition PASSES the per-element bars (this is what sets MARGIN); no bar
+    exceeds the per-tensor one; every mutant EXCEEDS the bar of every tensor it changes, on an element that has a bar."""
+    if case.amp != 1.0:
+        q, k, _, _ = ac.make_inputs(case)
+        assert (q[0, 0] @ k[0, 0].t() / math.sqrt(case.D)).abs().max() > 88.8          # exp(88.8) overflows fp32
+    for seed in ac.SEEDS:
+        o = ac.oracle(case, seed)
+        for name, got, want, bar, tbar in zip("qkv", _composition_with_grads(case, seed), o.grads, o.bars, o.tensor_bars):
+            assert bar.shape == want.shape and bar.dtype == torch.float64 and (bar <= tbar).all(), name
+            r = ac.ratio(got, want, bar)
+            print(f"ATBAR torch_fp32_composition {case.name} seed {seed} grad_{name} {r:.3f}")
+            assert r <= 1.0, (name, seed, r)
+        for mutant, grads in ac.mutants(case, seed).items():
+            for name, mut, want, bar, tbar in zip("qkv", grads, o.grads, o.bars, o.tensor_bars):
+                if ac.changed(mut, want, tbar):
+                    margin = ((mut - want).abs()[bar > 0] / bar[bar > 0]).max().item()
+                    print(f"ATMUT {mutant} {case.name} seed {seed} grad_{name} {margin:.1f}")
+                    assert margin > 1.0, (mutant, name, seed, margin)
+    if case.gout == "zero_rows":
+        o = ac.oracle(case)
+        assert (o.bars[0][:, :, -1] == 0).all() and (o.bars[2][..., 0] == 0).all() and (o.bars[1] > 0).all()
+
+
+def test_every_mutant_applies_somewhere_and_changes_what_it_should():
+    seen = {}
+    for case in ac.TABLE:
+        o = ac.oracle(case)
+        for mutant, grads in ac.mutants(case).items():
+            hit = seen.setdefault(mutant, set())
+            hit.update(n for n, mut, want, tbar in zip("qkv", grads, o.grads, o.tensor_bars) if ac.changed(mut, want, tbar))
+    assert sorted(seen) == ["1_last_key_left_out", "2_keys_32_63_left_out", "3_last_gout_row_zeroed", "4_one_gout_element_zeroed",
+                            "5_delta_omitted", "6_scale_missing_from_dq", "7_heads_of_k_swapped", "8_keep_ignored_in_backward",
+                            "9_keep_transposed_in_tile"]
+    assert seen.pop("5_delta_omitted") == {"q", "k"} and seen.pop("6_scale_missing_from_dq") == {"q"}
+    assert all(v == {"q", "k", "v"} for v in seen.values()), seen
+
+
+@pytest.mark.parametrize("name,seed,mutant,tensor", [("w200_66x3", 1, "4_one_gout_element_zeroed", 1),
+                                                     ("m32_65x130_amp80", 0, "1_last_key_left_out", 0)])
+def test_the_per_tensor_bars_miss_what_the_per_element_bars_catch(name, seed, mutant, tensor):
+    """Why the per-element bars exist: one zeroed grad_out element moves grad_k of w200_66x3 by at most 0.28 of its
+    per-tensor bar, a left-out key grad_q of m32_65x130_amp80 by 0.22 of it."""
+    case = ac.by_name(name)
+    o = ac.oracle(case, seed)
+    d = (ac.mutants(case, seed)[mutant][tensor] - o.grads[tensor]).abs()
+    assert d.max().item() <= o.tensor_bars[tensor]
+    assert (d > o.bars[tensor]).any()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("case", ac.TABLE, ids=lambda c: c.name)
+def test_host_path_on_the_table(case, dtype):
+    """The host path on every case, in the case's layout and grad_out form: fp32 within fp32_bar and the per-element
+    gradient bars, fp64 at 1e-12 / 1e-11; a strided run is bit-equal to the dense one."""
+    op = _ops()
+    out, grads, _, _ = ac.run(op, case, dtype=dtype)
+    if dtype == torch.float64:
+        ac.check_fp64(case, out, grads)
+    else:
+        ac.check_out(case, out, "host_path")
+        ac.check_grads(case, grads, "host_path")
+    if case.layout != "dense" or case.gout in ("expanded", "misaligned"):
+        ref_out, ref_grads, _, _ = ac.run(op, case, dtype=dtype, layout="dense", gout="proj")
+        assert torch.equal(out, ref_out)
+        for a, b in zip(grads, ref_grads):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("case", [c for c in ac.TABLE if c.layout != "dense"], ids=lambda c: c.name)
+def test_table_layouts_reach_the_entry_point_in_place(case):
+    """The head-split views of the table are what the library is handed (no dense copy), and out lies in memory like q."""
+    op = _ops()
+    x = ac.lay_out(case)
+    out = op.attention(x.q, x.k, x.v)
+    for view, reached in zip((x.q, x.k, x.v), out.grad_fn.saved_tensors[:3]):
+        assert reached.data_ptr() == view.data_ptr() and reached.stride() == view.stride()
+    assert len({t.data_ptr() for t in (x.q, x.k, x.v)}) == 3 and len(x.leaves) == (1 if case.Sq == case.Sk else 2)
+    assert out.permute((0, 2, 1, 3) if case.layout == "batch_first" else (2, 0, 1, 3)).is_contiguous()
+    assert x.gout.permute((0, 2, 1, 3) if case.layout == "batch_first" else (2, 0, 1, 3)).is_contiguous()
 
 
 def test_bad_calls_raise_clear_errors():
@@ -243,6 +354,57 @@ def test_module_is_nn_multihead_attention(batch_first):
     for kw in (dict(need_weights=True), dict(key_padding_mask=mask, need_weights=False), dict(key_padding_mask=mask)):
         a, b = ours(x, x, y, **kw), theirs(x, x, y, **kw)
         assert torch.equal(a[0], b[0]) and (a[1] is None) == (b[1] is None) and (a[1] is None or torch.equal(a[1], b[1]))
+
+
+def module_against_fp64_torch(E, heads, batch_first, device, routes=None):
+    """ops.MultiheadAttention (fp32, eval, on ``device``) against fp64 nn.MultiheadAttention on the CPU with the same state
+    dict: output, every parameter gradient and the input gradients within _module_bar, for (x, x, x), (x, x, y) and
+    (x, y, z) with 70 queries and, in the cross case, 33 keys.  ``routes``: the (forward, backward) last_kernel() names."""
+    from mvdetr_amd.ops import MultiheadAttention
+    torch.manual_seed(3)
+    theirs = nn.MultiheadAttention(E, heads, batch_first=batch_first).double().eval()
+    with torch.no_grad():
+        for p in theirs.parameters():
+            p.normal_(0, 0.3)
+    ours = MultiheadAttention(E, heads, batch_first=batch_first).eval()
+    ours.load_state_dict({k: v.float() for k, v in theirs.state_dict().items()}, strict=True)
+    ours.to(device)
+    g = torch.Generator().manual_seed(8)
+
+    def tokens(S):
+        return torch.randn((2, S, E) if batch_first else (S, 2, E), generator=g)
+    x, y, yk, zv = tokens(70), tokens(70), tokens(33), tokens(33)
+    worst = 0.0
+    for args in ((x, x, x), (x, x, y), (x, yk, zv)):
+        leaves = {id(a): a for a in args}                              # (x, x, x) stays ONE tensor: `query is key`
+        dev = {i: a.clone().to(device).requires_grad_(True) for i, a in leaves.items()}
+        ref = {i: a.double().requires_grad_(True) for i, a in leaves.items()}
+        got, none = ours(*(dev[id(a)] for a in args), need_weights=False)
+        assert none is None
+        if routes:
+            assert _ops().last_kernel() == routes[0]
+        want = theirs(*(ref[id(a)] for a in args), need_weights=False)[0]
+        gout = torch.randn(want.shape, generator=g)
+        ours.zero_grad()
+        theirs.zero_grad()
+        got.backward(gout.to(device))
+        if routes:
+            assert _ops().last_kernel() == routes[1]
+        want.backward(gout.double())
+        pairs = [("out", got.detach(), want.detach())]
+        pairs += [(n, a.grad, b.grad) for (n, a), b in zip(ours.named_parameters(), theirs.parameters())]
+        pairs += [(f"input{j}", dev[i].grad, ref[i].grad) for j, i in enumerate(leaves)]
+        for n, a, b in pairs:
+            r = (a.cpu().double() - b).abs().max().item() / _module_bar(b)
+            worst = max(worst, r)
+            assert r <= 1.0, (n, len(leaves), r)
+    print(f"module E {E} heads {heads} batch_first {batch_first} on {device}: worst err / bar = {worst:.3f}")
+
+
+@pytest.mark.parametrize("batch_first", [False, True])
+@pytest.mark.parametrize("E,heads", [(64, 4), (40, 2)])
+def test_module_against_fp64_nn_multihead_attention(E, heads, batch_first):
+    module_against_fp64_torch(E, heads, batch_first, "cpu")
 
 
 # ---- the aggregator and the model -------------------------------------------------------------------------------------------

@@ -1,8 +1,11 @@
 """Fused multi-head attention on the MI355X: the MFMA and the generic kernels of csrc/attention.hip against the fp64 oracle,
 within the bars of attention_oracle (see tests/test_attention.py), with the route pinned by last_kernel(); determinism,
-dropout, peak memory, streams; the trans aggregator and model on the device against the CPU host path.
+dropout, peak memory, streams; the trans aggregator and model on the device against the CPU host path.  The case table of
+attention_cases.py (MFMA tile edges, strided layouts, grad_out forms, wide heads, fp64, dropout, large logits) runs with
+the per-element gradient bars; every ``ATBAR route case tensor err/bar`` line is a figure of DESIGN.md section 4.8.
 
-Each fp64 oracle case is evaluated once per module (``_oracle``)."""
+Each fp64 oracle case is evaluated once per module (``_oracle``, ``attention_cases.oracle``)."""
+import ctypes
 import functools
 import importlib
 import math
@@ -10,6 +13,7 @@ import math
 import pytest
 import torch
 
+import attention_cases as ac
 import attention_oracle as ao
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +51,11 @@ def _oracle(size, seed=0, amp=1.0):
 def _oracle_grads(size, seed=0):
     q, k, v, gout = _inputs(size, seed)
     return ao.with_grads(q, k, v, gout)[1:], ao.grad_bars(q, k, v, gout)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_grad_bars_elementwise(size, seed=0):
+    return ao.grad_bars_elementwise(*_inputs(size, seed))
 
 
 def _forward_check(size, want_kernel, seed=0, amp=1.0, layout="dense"):
@@ -141,6 +150,11 @@ def _backward_check(size, want_kernel):
         print(f"{want_kernel} {size} grad_{name}: err / bar = {err / bar:.3f}")
         assert err <= bar, (name, err, bar)
         assert b.abs().max().item() > 0, name
+    if max(size[2:4]) <= 130:                             # the small shapes: per element as well
+        for name, a, b, bar in zip("qkv", leaves, want, _oracle_grad_bars_elementwise(size)):
+            r = ac.ratio(a.grad.cpu(), b, bar)
+            print(f"ATBAR {want_kernel} {size} grad_{name} {r:.3f}")
+            assert r <= 1.0, (name, r)
 
 
 @pytest.mark.parametrize("size", [WILDTRACK, STRESS16, (2, 3, 12, 130, 16), (1, 2, 63, 64, 32), (2, 2, 65, 12, 16), (1, 2, 130, 65, 32)])
@@ -151,6 +165,76 @@ def test_backward_mfma(size):
 @pytest.mark.parametrize("size", [(2, 3, 65, 130, 4), (1, 2, 12, 63, 20), (1, 2, 130, 65, 64)])
 def test_backward_generic(size):
     _backward_check(size, "attn_bwd_generic")
+
+
+# ---- the case table -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("case", ac.TABLE, ids=lambda c: c.name)
+def test_table_on_the_device(case):
+    """Every case in its own layout and grad_out form: routes pinned after the forward and after the backward, out within
+    fp32_bar, gradients within the per-element (and per-tensor) bars; fp64 cases at 1e-12 / 1e-11."""
+    out, grads, fwd, bwd = ac.run(_ops(), case, DEV)
+    assert (fwd, bwd) == ("attn_" + case.fwd, "attn_" + case.bwd)
+    if case.dtype == torch.float64:
+        ac.check_fp64(case, out, grads)
+    else:
+        ac.check_out(case, out, fwd)
+        ac.check_grads(case, grads, bwd)
+
+
+@pytest.mark.parametrize("case", [c for c in ac.TABLE if c.layout != "dense" or c.gout == "expanded"], ids=lambda c: c.name)
+def test_strided_layouts_equal_the_dense_run(case):
+    """The kernels' arithmetic does not depend on addresses: packed / split, seq-first / batch-first operands and an
+    expanded grad_out give the bits of the dense run.  (The misaligned grad_out takes another backward route than the
+    dense run, attn_bwd_generic after attn_fwd_mfma: it has the oracle's bars in test_table_on_the_device only.)"""
+    out, grads, fwd, bwd = ac.run(_ops(), case, DEV)
+    ref_out, ref_grads, ref_fwd, ref_bwd = ac.run(_ops(), case, DEV, layout="dense", gout="proj")
+    assert (fwd, bwd) == (ref_fwd, ref_bwd) == ("attn_" + case.fwd, "attn_" + case.bwd)
+    assert torch.equal(out, ref_out)
+    for name, a, b in zip("qkv", grads, ref_grads):
+        assert torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("D,fwd,bwd", [(16, "attn_fwd_mfma", "attn_bwd_mfma"), (65, "attn_fwd_generic", "attn_bwd_generic")])
+def test_padded_outputs_through_the_c_entry_points(D, fwd, bwd):
+    """out, grad_q, grad_k, grad_v with a token stride of D + 4 in NaN-filled buffers: the rows are the op's bit for bit
+    and no pad element is written (attn_store_acc's d0 < D on the MFMA route, lane + 64 c < D on the generic one)."""
+    from mvdetr_amd import _lib
+    op, lib = _ops(), _lib.lib()
+    B, H, Sq, Sk = 2, 2, 33, 97
+    g = torch.Generator().manual_seed(D)
+    q, k, v, gout = (torch.randn(B, H, S, D, generator=g).to(DEV) for S in (Sq, Sk, Sk, Sq))
+    leaves = [x.clone().requires_grad_(True) for x in (q, k, v)]
+    ref = op.attention(*leaves)
+    ref.backward(gout)
+    assert op.last_kernel() == bwd
+    bufs = [torch.full((B, H, S, D + 4), float("nan"), device=DEV) for S in (Sq, Sq, Sk, Sk)]      # out, gq, gk, gv
+    out, gq, gk, gv = bufs
+    lse = torch.empty(B, H, Sq, device=DEV)
+    stream = _lib.current_stream_ptr(q.device)
+
+    def strides(*tensors):
+        flat = [s for t in tensors for s in t.stride()[:3]]
+        return (ctypes.c_int64 * len(flat))(*flat)
+    rc = lib.mvdetr_attention_forward_f32(stream, q.data_ptr(), k.data_ptr(), v.data_ptr(), strides(q, k, v, out), B, H, Sq, Sk, D,
+                                          0.0, 0, out.data_ptr(), lse.data_ptr())
+    assert rc == 0 and op.last_kernel() == fwd
+    work = torch.empty(lib.mvdetr_attention_workspace_bytes(B, H, Sq, Sk, D, 4), dtype=torch.uint8, device=DEV)
+    rc = lib.mvdetr_attention_backward_f32(stream, gout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                           lse.data_ptr(), strides(q, k, v, out, gout, gq, gk, gv), B, H, Sq, Sk, D, 0.0, 0,
+                                           work.data_ptr(), gq.data_ptr(), gk.data_ptr(), gv.data_ptr())
+    assert rc == 0 and op.last_kernel() == bwd
+    torch.cuda.synchronize()
+    for name, buf, want in zip(("out", "grad_q", "grad_k", "grad_v"), bufs, (ref.detach(), *(x.grad for x in leaves))):
+        assert torch.equal(buf[..., :D], want), name
+        assert torch.isnan(buf[..., D:]).all(), name
+
+
+@pytest.mark.parametrize("batch_first", [False, True])
+@pytest.mark.parametrize("E,heads,routes", [(64, 4, ("attn_fwd_mfma", "attn_bwd_mfma")), (40, 2, ("attn_fwd_generic", "attn_bwd_generic"))])
+def test_module_on_the_device_is_fp64_nn_multihead_attention(E, heads, routes, batch_first):
+    from test_attention import module_against_fp64_torch
+    module_against_fp64_torch(E, heads, batch_first, DEV, routes)
 
 
 def test_device_fp64_gradcheck():
