@@ -488,6 +488,23 @@ int mvdetr_attention_backward_f64(void *stream, const double *grad_out, const do
                                   const double *out, const double *lse, const int64_t *strides, int batch, int heads, int sq,
                                   int sk, int head_dim, double dropout_p, uint64_t seed, void *workspace, double *grad_q,
                                   double *grad_k, double *grad_v);
+/* 16-bit storage variants of the forward (inference; an addition, the ABI version above is unchanged): q, k, v, out are IEEE
+ * binary16 (_f16) or bfloat16 (_bf16) as raw 16-bit words, addressed by the same 12 ELEMENT strides as above.  Forward only: no
+ * dropout, no lse, no masks.  One kernel, "attn_fwd_mfma_half" (csrc/attention_half.hip): S = Q K^T on the 16-bit MFMA is
+ * exactly the fp32 kernel's S of the upcast inputs (fp32 accumulator); softmax, running maximum and sum, rescale and 1 / l are
+ * fp32; the probabilities enter the P V product as TWO 16-bit terms (hi = rn16(P), lo = rn16(P - hi)), which leaves 2^-18 (bf16)
+ * / 2^-22 (f16) of P; out is rounded once, to nearest even.  No atomics: bit-reproducible run to run.
+ * head_dim must be 16 or 32, sk >= 1, every base pointer 16-byte aligned and every stride a multiple of 8 elements (each row
+ * starts 16-byte aligned), batch and heads <= 65535: hipErrorNotSupported (801) otherwise, and no kernel is launched (the
+ * caller upcasts and takes the fp32 entry).  batch * heads * sq == 0 returns 0 without a launch. */
+int mvdetr_attn_forward_f16(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides,
+                            int batch, int heads, int sq, int sk, int head_dim, uint16_t *out);
+int mvdetr_attn_forward_bf16(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides,
+                             int batch, int heads, int sq, int sk, int head_dim, uint16_t *out);
+/* Queries per workgroup of attn_fwd_mfma_half: 64, 128, or 0 = chosen by the shape (the default: 128 unless sq <= 64).  The
+ * results do not depend on it.  Process-wide; returns the previous value, -1 (and changes
+ * nothing) for any other argument.  For tests and tools. */
+int mvdetr_attn_half_set_query_tile(int queries);
 /* Name of the kernel route the last device attention call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_attention_last_kernel(void);
 

@@ -133,6 +133,9 @@ SIGNATURES = {
     "mvdetr_attention_workspace_bytes": ([_i] * 6, ctypes.c_int64),
     "mvdetr_attention_forward_f32": (_ATTN_FWD, _i),
     "mvdetr_attention_forward_f64": (_ATTN_FWD, _i),
+    "mvdetr_attn_forward_f16": ([_vp] * 4 + [_i64p] + [_i] * 5 + [_vp], _i),
+    "mvdetr_attn_forward_bf16": ([_vp] * 4 + [_i64p] + [_i] * 5 + [_vp], _i),
+    "mvdetr_attn_half_set_query_tile": ([_i], _i),
     "mvdetr_attention_backward_f32": (_ATTN_BWD, _i),
     "mvdetr_attention_backward_f64": (_ATTN_BWD, _i),
     "mvdetr_attention_forward_host_f32": (_ATTN_FWD[1:], _i),

@@ -20,6 +20,7 @@
 //                   attn_bwd_dkv_mfma   a wave owns 32 keys (lane = key) and loops over query tiles:  S = Q K^T, dP = dO V^T,
 //                                       dV^T += dO^T P, dK^T += Q^T dS.
 //                   Every output element is owned by one lane: NO atomics, bit-reproducible run to run.
+//   attn_fwd_mfma_half   fp16 / bf16 storage, forward only: attention_half.hip.
 //   attn_fwd_generic / attn_bwd_generic   any D <= 256, fp32 and fp64, any alignment: one wave per query row (forward, dQ) or
 //                   per key row (dK, dV), 64 scores at a time through LDS; same determinism.
 // Dropout (template parameter, absent from the p = 0 instantiations): element (b, h, i, j) is kept iff
@@ -37,7 +38,7 @@
 
 namespace mvdetr {
 
-static std::atomic<const char *> g_attn_last_kernel{"none"};
+std::atomic<const char *> g_attn_last_kernel{"none"};          // (attention_half.hip sets it too)
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 

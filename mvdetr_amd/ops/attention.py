@@ -7,6 +7,12 @@ ever writing a score: CUDA tensors run the HIP kernels of csrc/attention.hip (fp
 kernels, everything else the generic ones), CPU tensors the library's host path.  The backward recomputes the
 probabilities from the saved log-sum-exp, uses no atomics and is bit-reproducible run to run.
 
+16-bit inference: CUDA float16 / bfloat16 q, k, v with ``dropout_p == 0`` and nothing to differentiate run
+``attn_fwd_mfma_half`` (csrc/attention_half.hip: 16-bit MFMA, fp32 softmax, the probabilities as two 16-bit terms, one
+rounding on the way out) when the head dimension is 16 or 32 and every row starts 16-byte aligned; every other such call
+is ``attention(q.float(), k.float(), v.float()).to(dtype)`` on the fp32 kernels.  A 16-bit call that needs gradients or
+dropout is refused, and there is no 16-bit host path.
+
 * ``attention(q, k, v, dropout_p=0.0, seed=None)``: q [B, H, Sq, D], k and v [B, H, Sk, D] -> [B, H, Sq, D].  The operands
   may be any views whose last dimension is contiguous (a head-split view of a seq-first or batch-first projection is read in
   place).  Dropout acts on the probabilities as in torch, by a counter-based hash of (seed, element index)
@@ -31,8 +37,17 @@ MAX_HEAD_DIM = 256
 
 def last_kernel() -> str:
     """Route of the last attention call of this process on the device: "attn_fwd_mfma", "attn_fwd_generic",
-    "attn_bwd_mfma" or "attn_bwd_generic" (tests / tools introspection)."""
+    "attn_bwd_mfma", "attn_bwd_generic" or "attn_fwd_mfma_half" (tests / tools introspection)."""
     return _lib.lib().mvdetr_attention_last_kernel().decode()
+
+
+def set_half_query_tile(queries: int) -> int:
+    """Queries per workgroup of the 16-bit kernel: 64, 128 or 0 (by the shape, the default); returns the previous value.  The
+    results do not depend on it (tests / tools)."""
+    prev = _lib.lib().mvdetr_attn_half_set_query_tile(int(queries))
+    if prev < 0:
+        raise ValueError(f"set_half_query_tile: 0, 64 or 128, got {queries}")
+    return prev
 
 
 def dropout_keep_mask(seed: int, p: float, B: int, H: int, Sq: int, Sk: int) -> torch.Tensor:
@@ -112,6 +127,30 @@ class AttentionFunction(Function):
         return gq, gk, gv, None, None
 
 
+HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _half_rows_ok(t) -> bool:
+    """Can attn_fwd_mfma_half read this view in place?  Every row 16-byte aligned: base and strides (in elements, % 8)."""
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:3])
+
+
+def _attention_half(q, k, v):
+    """The 16-bit forward (inference only; the caller has checked dtype, device, dropout and grad)."""
+    B, H, Sq, D = q.shape
+    if D in (16, 32) and B <= 65535 and H <= 65535 and all(_half_rows_ok(t) for t in (q, k, v)):
+        out = _empty_like_order(q)
+        if out.numel() and _half_rows_ok(out):
+            with torch.cuda.device(q.device):
+                rc = getattr(_lib.lib(), f"mvdetr_attn_forward_{_lib.suffix(q.dtype, half_ok=True)}")(
+                    _lib.current_stream_ptr(q.device), q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v, out),
+                    B, H, Sq, k.shape[2], D, out.data_ptr())
+            _lib.check(rc, "attention_forward_half")
+            return out
+    # what the 16-bit kernel does not take (another head dimension, rows off alignment): the fp32 kernels on the upcast
+    return attention(q.float(), k.float(), v.float()).to(q.dtype)
+
+
 def attention(q, k, v, dropout_p=0.0, seed=None):
     """softmax(q k^T / sqrt(D)) v per (batch, head): q [B, H, Sq, D], k and v [B, H, Sk, D] -> [B, H, Sq, D] (laid out in
     memory like q).  ``dropout_p`` in [0, 1) drops probabilities (kept ones scaled by 1 / (1 - p)); ``seed``: 64-bit
@@ -125,7 +164,8 @@ def attention(q, k, v, dropout_p=0.0, seed=None):
     dtypes = {t.dtype for t in (q, k, v)}
     if len(dtypes) != 1:
         raise RuntimeError(f"attention: all tensors must have one dtype, got {sorted(map(str, dtypes))}")
-    _lib.suffix(q.dtype)                                           # 16-bit dtypes raise here
+    half = q.dtype in HALF_DTYPES and q.is_cuda
+    _lib.suffix(q.dtype, half_ok=half)                             # 16-bit CPU tensors raise here
     B, H, Sq, D = q.shape
     if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
         raise ValueError(f"attention: k {tuple(k.shape)} and v {tuple(v.shape)} must both be [B, H, Sk, D] for q "
@@ -137,6 +177,13 @@ def attention(q, k, v, dropout_p=0.0, seed=None):
     dropout_p = float(dropout_p)
     if not 0.0 <= dropout_p < 1.0:
         raise ValueError(f"attention: dropout_p must be in [0, 1), got {dropout_p}")
+    if half:
+        if dropout_p != 0.0:
+            raise ValueError(f"attention: the {q.dtype} kernel is inference-only and has no dropout (dropout_p = {dropout_p})")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+            raise RuntimeError(f"attention: the {q.dtype} kernel is forward-only (inference); run it under torch.no_grad() "
+                               f"or on tensors that do not require grad")
+        return _attention_half(q, k, v)
     if dropout_p == 0.0:
         seed = 0
     elif seed is None:
@@ -150,14 +197,24 @@ class MultiheadAttention(nn.MultiheadAttention):
     signature and return pair.  With ``need_weights=False``, no masks, ``bias=True``, equal embedding sizes, 3-D fp32 / fp64
     inputs it returns ``(out, None)`` from in-projection GEMM(s) (one for q and k when ``query is key``) -> ``attention`` ->
     out-projection, the heads read from the projections in place.  Every other call (weights requested, masks, kdim / vdim,
-    add_bias_kv, add_zero_attn, unbatched or 16-bit inputs, is_causal) is torch's own implementation, unchanged."""
+    add_bias_kv, add_zero_attn, unbatched inputs, is_causal) is torch's own implementation, unchanged.  16-bit (float16 /
+    bfloat16) CUDA inputs take the same route in eval mode when nothing needs a gradient (``attention`` is forward-only in
+    16 bits); a training-mode or differentiated 16-bit call is torch's implementation."""
+
+    def _dtype_ok(self, query, key, value):
+        if query.dtype in (torch.float32, torch.float64):
+            return True
+        if query.dtype not in HALF_DTYPES or not query.is_cuda or self.training:
+            return False
+        return not (torch.is_grad_enabled() and (any(t.requires_grad for t in (query, key, value))
+                                                 or any(p.requires_grad for p in self.parameters())))
 
     def _fused_ok(self, query, key, value, key_padding_mask, need_weights, attn_mask, kw):
         return (not need_weights and key_padding_mask is None and attn_mask is None and not kw.get("is_causal", False)
                 and self._qkv_same_embed_dim and self.in_proj_bias is not None and self.bias_k is None
                 and self.bias_v is None and not self.add_zero_attn and query.dim() == 3 and key.dim() == 3
                 and value.dim() == 3 and key.shape == value.shape
-                and query.dtype in (torch.float32, torch.float64) and query.dtype == key.dtype == value.dtype
+                and self._dtype_ok(query, key, value) and query.dtype == key.dtype == value.dtype
                 and query.dtype == self.in_proj_weight.dtype and query.device == key.device == value.device
                 and self.head_dim <= MAX_HEAD_DIM and key.shape[0 if not self.batch_first else 1] > 0
                 and not torch.is_autocast_enabled())

@@ -282,7 +282,10 @@ class DeformConvWorldFeat(nn.Module):
 class TransformerEncoderLayer(nn.Module):
     """The DETR encoder layer of the reference's ``trans`` aggregator (models/transformer.py:37-65): post-norm,
     ``q = k = src + pos``, ``value = src``; tokens seq-first [S, B, C].  ``self_attn`` is ops.MultiheadAttention (state-dict
-    compatible with nn.MultiheadAttention), called without weights: the fused kernels of csrc/attention.hip."""
+    compatible with nn.MultiheadAttention), called without weights: the fused kernels of csrc/attention.hip.  16-bit
+    inference (float16 / bfloat16 CUDA tokens, eval mode): the attention core is attn_fwd_mfma_half and both add + LayerNorm
+    tails are one HIP pass each, rounded once (torch's add, then LayerNorm, rounds twice); fp32 / fp64 calls keep torch's
+    ops for the tails bit for bit."""
 
     def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1):
         super().__init__()
@@ -305,6 +308,10 @@ class TransformerEncoderLayer(nn.Module):
         fused = src_mask is None and src_key_padding_mask is None
         src2 = self.self_attn(q, k, value=src, attn_mask=src_mask, key_padding_mask=src_key_padding_mask,
                               need_weights=not fused)[0]
+        if (not self.training and src.is_cuda and src.dtype in (torch.float16, torch.bfloat16)
+                and fused_add_layer_norm_available(src, self.norm1) and fused_add_layer_norm_available(src, self.norm2)):
+            src = add_layer_norm(src2, src, self.norm1)
+            return add_layer_norm(self.linear2(F.relu(self.linear1(src))), src, self.norm2)
         src = self.norm1(src + self.dropout1(src2))
         src2 = self.linear2(self.dropout(F.relu(self.linear1(src))))
         return self.norm2(src + self.dropout2(src2))

@@ -7,9 +7,14 @@ torch runs for the same op, interleaved in one process:
              as the reference calls it (need_weights left True: the weights are materialised and averaged) and with
              need_weights=False (torch then takes F.scaled_dot_product_attention);
   aggregator TransformerWorldFeat per frame (eval) and the peak memory of one training step vs the same module with
-             nn.MultiheadAttention swapped in, both ways.
+             nn.MultiheadAttention swapped in, both ways;
+  core half  (--half-runs R: R runs of this row alone, nothing else) the 16-bit forward attn_fwd_mfma_half in bfloat16 and
+             float16 on the head-split views of one seq-first packed [S, B, 3E] projection, with 64 and with 128 queries per
+             workgroup and as the library picks, vs the fp32 attn_fwd_mfma on the same values, vs the upcast fallback
+             (attention(q.float(), k.float(), v.float()).to(dtype)), vs what nn.MultiheadAttention runs in 16 bits
+             (F.scaled_dot_product_attention with need_weights=False, bmm / softmax / bmm as the reference calls it).
 
-    python tools/attention_bench.py [--reps N] [--sizes wildtrack,multiviewx,stress16,wildtrack_b4]
+    python tools/attention_bench.py [--reps N] [--sizes wildtrack,multiviewx,stress16,wildtrack_b4] [--half-runs R]
 
 Every figure is the median of N (>= 20) device-event times after warm-up, with the spread (min .. max) beside it; the
 implementations of one row are timed alternately, repetition by repetition.  TF/s counts 4 B H Sq Sk D FLOP forward and 2.5 x
@@ -100,6 +105,44 @@ def bench_core(name, reps, rows):
     torch.autograd.grad(attention_op(q, k, v), (q, k, v), gout)
     extra = {"kernel": last_kernel()}
     emit(rows, "core fwd+bwd", name, interleaved({n: fwd_bwd(f) for n, f in impls.items()}, reps), 2.5 * flop, extra)
+
+
+def bench_core_half(name, reps, rows, run):
+    """The 16-bit forward at one size: every implementation on the same values, interleaved."""
+    from mvdetr_amd.ops import attention as attention_op
+    from mvdetr_amd.ops.attention import last_kernel, set_half_query_tile
+    B, H, S, D = SIZES[name]
+    E = H * D
+    dev = torch.device("cuda:0")
+    proj32 = torch.randn(S, B, 3 * E, generator=torch.Generator().manual_seed(0)).to(dev)
+
+    def heads(proj):
+        return [t.unflatten(-1, (H, D)).permute(1, 2, 0, 3) for t in proj.split(E, dim=-1)]
+
+    def tiled(tile, qkv):
+        def run_():
+            set_half_query_tile(tile)
+            attention_op(*qkv)
+            set_half_query_tile(0)
+        return run_
+    flop = 4.0 * B * H * S * S * D
+    with torch.no_grad():
+        for dtype in (torch.bfloat16, torch.float16):
+            proj = proj32.to(dtype)
+            qkv = heads(proj)
+            qkv32 = heads(proj.float())                      # the same values in fp32
+            got = attention_op(*qkv)
+            kern = last_kernel()
+            diff = (got.float() - attention_op(*qkv32)).abs().max().item()
+            fns = {"hip": lambda qkv=qkv: attention_op(*qkv), "hip_tq64": tiled(64, qkv), "hip_tq128": tiled(128, qkv),
+                   "hip_fp32_same_values": lambda qkv32=qkv32: attention_op(*qkv32),
+                   "hip_upcast_fallback": lambda qkv=qkv, dtype=dtype: attention_op(*(t.float() for t in qkv)).to(dtype),
+                   "torch_sdpa_16bit": lambda qkv=qkv: sdpa(*qkv)}
+            extra = {"kernel": kern, "dtype": str(dtype)[6:], "run": run, "max_abs_diff_vs_fp32_kernel": diff}
+            emit(rows, f"core half fwd {str(dtype)[6:]}", name, interleaved(fns, reps), flop, extra)
+            # a rotation of its own: the composition writes 2 x B H S S scores, and whatever runs after it starts on cold caches
+            pair = {"hip": fns["hip"], "torch_bmm_softmax_bmm_16bit": lambda qkv=qkv: torch_composition(*qkv)}
+            emit(rows, f"core half fwd {str(dtype)[6:]} (after the composition)", name, interleaved(pair, reps), flop, extra)
 
 
 def bench_module(name, reps, rows):
@@ -195,6 +238,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sizes", default="wildtrack,multiviewx,stress16,wildtrack_b4")
+    ap.add_argument("--half-runs", type=int, default=0, help="run only the 16-bit forward row, this many times")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("attention_bench: needs a GPU (no CPU fallback for timings)")
@@ -215,19 +259,23 @@ def main():
     print(f"# F.scaled_dot_product_attention backends that accept fp32 here (torch picks among them): {backends}")
     rows = []
     for name in a.sizes.split(","):
+        if a.half_runs:
+            for run in range(a.half_runs):
+                bench_core_half(name, reps, rows, run)
+            continue
         bench_core(name, reps, rows)
         bench_module(name, reps, rows)
         if name in GRIDS:
             bench_aggregator(name, reps, rows)
         torch.cuda.empty_cache()
-    print(f"\n{'what':<34} {'size':<13} {'impl':<27} {'median us':>10} {'min':>9} {'max':>9} {'TF/s':>7} {'% peak':>7} {'hip x':>6}")
+    print(f"\n{'what':<50} {'size':<13} {'impl':<27} {'median us':>10} {'min':>9} {'max':>9} {'TF/s':>7} {'% peak':>7} {'hip x':>6}")
     for r in rows:
         if "median_us" in r:
             tf = f"{r['tflops']:>7.2f} {100 * r['frac_of_peak']:>6.1f}%" if "tflops" in r else f"{'':>7} {'':>7}"
-            print(f"{r['what']:<34} {r['size']:<13} {r['impl']:<27} {r['median_us']:>10.1f} {r['min_us']:>9.1f} {r['max_us']:>9.1f} "
+            print(f"{r['what']:<50} {r['size']:<13} {r['impl']:<27} {r['median_us']:>10.1f} {r['min_us']:>9.1f} {r['max_us']:>9.1f} "
                   f"{tf} {r['speedup_of_hip']:>6.2f}")
         else:
-            print(f"{r['what']:<34} {r['size']:<13} {r['impl']:<27} {r['peak_mib']:>10.1f} MiB")
+            print(f"{r['what']:<50} {r['size']:<13} {r['impl']:<27} {r['peak_mib']:>10.1f} MiB")
 
 
 if __name__ == "__main__":

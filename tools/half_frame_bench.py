@@ -7,6 +7,8 @@ repetition by repetition (same call, alternating, spread first):
   msda            the fused deformable-attention forward alone on the encoder's input
                   (msda_fwd_group2 / msda_fwd_fused_half);
   add_layernorm   ops.add_layer_norm alone with the second output, 75,600 rows x 128;
+  trans           a whole frame (MVDeTr.detect) of the ``trans`` world feature: the encoder's attention core is attn_fwd_mfma in
+                  float32 and attn_fwd_mfma_half in 16 bits (models of its own, built only when the row is asked for);
 
 each for float32, bfloat16 and float16; then, for each 16-bit variant,
 
@@ -88,7 +90,7 @@ def detection_cells(model, imgs, M, thres):
     return set(det.cell[0, :min(n, det.cell.shape[1])].tolist())
 
 
-ROWS = ("detect", "hot_path", "warp", "msda", "add_layernorm", "trunk", "trunk_kernels", "detections")
+ROWS = ("detect", "hot_path", "warp", "msda", "add_layernorm", "trans", "trunk", "trunk_kernels", "detections")
 
 
 def trunk_kernel_launches(views, feat_hw, dtype, device):
@@ -190,6 +192,16 @@ def main():
             kernels["msda"][name] = MSDA.last_forward_kernel()
             fns["hot_path"][name]()
             kernels["hot_path"][name] = f"{warp_mod.last_kernel()} + {MSDA.last_forward_kernel()}"
+
+        if "trans" in only:
+            from mvdetr_amd.ops.attention import last_kernel as attn_last_kernel
+            fns["trans"], kernels["trans"] = {}, {}
+            for name, dtype in VARIANTS.items():
+                m = build_model(a.config, seed=0, world_feat_arch="trans").to(DEV).eval()
+                m = m if dtype is None else m.to_inference(dtype)
+                fns["trans"][name] = lambda m=m: m.detect(imgs, M)
+                fns["trans"][name]()
+                kernels["trans"][name] = f"{warp_mod.last_kernel()} + {attn_last_kernel()}"
 
         rows = []
         for what, variants in fns.items():
