@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16 (purely additive again) */
+#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -357,6 +357,27 @@ int mvdetr_bn_relu_maxpool_bf16(void *stream, const uint16_t *x, const float *me
  * many such launches there have been: tests tell the fused path from torch's ops by them.  Static storage; never NULL. */
 const char *mvdetr_trunk_last_kernel(void);
 int64_t mvdetr_trunk_launch_count(void);
+
+/* ---- Winograd F(2x2, 3x3) convolution in fp32 (csrc/conv_winograd.hip; additive entries) -----------------------
+ * A 3x3 convolution with stride 1, padding = dilation, groups 1 and no bias over channel-last fp32 activations, as
+ *     Y = A^T [ sum_c (G g G^T) .* (B^T d B) ] A     per 2x2 output tile
+ * with the sixteen products over the input channels on the fp32 MFMA (2.25x fewer multiplications than the direct
+ * form; fp32 inputs, products and sums throughout).  Two steps:
+ *   mvdetr_winograd_weights_f32   w [K, C, 3, 3] dense (OIHW) -> U [16, C, K]: G g G^T formed in fp64 and rounded once.
+ *                                 Runs once per weight tensor (C * K threads).
+ *   mvdetr_conv3x3_winograd_f32   x [N, H, W, C] -> y [N, H, W, K] (NHWC memory, y fresh: it may not be x), one launch;
+ *                                 x and U are only read, every element of y is written once, nothing outside it; no
+ *                                 atomics: bit-reproducible.  A dilation d runs as d * d undilated convolutions on the
+ *                                 pixel sub-lattices (y mod d, x mod d), in place.
+ * Contract: C % 8 == 0, K % 64 == 0, dilation 1, 2 or 4, 16-byte aligned x, U, y, (256 + 2 H W) max(C, K) < 2^30,
+ * fewer than 2^31 tiles: hipErrorNotSupported (801) otherwise, hipErrorInvalidValue for null pointers / sizes <= 0.
+ * Kernel names: "winograd_weights_f32", "conv3x3_winograd_f32". */
+int mvdetr_winograd_weights_f32(const float *w, int C, int K, float *U, void *stream);
+int mvdetr_conv3x3_winograd_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K, int dilation,
+                                void *stream);
+/* Name of the kernel the last call of the two above launched ("none" before the first) and their launch count. */
+const char *mvdetr_winograd_last_kernel(void);
+int64_t mvdetr_winograd_launch_count(void);
 
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------
  * Name of the kernel variant the last forward call ON THIS THREAD dispatched to

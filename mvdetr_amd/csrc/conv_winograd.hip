@@ -1,0 +1,324 @@
+// Winograd F(2x2, 3x3) convolution in exact fp32 on the MFMA units, for the ResNet trunk's wide 3x3 convolutions
+// (stride 1, padding = dilation, no bias, channel-last activations).
+//
+//   Y = A^T [ sum_c (G g G^T) .* (B^T d B) ] A          per 2x2 output tile and output channel
+//
+// The sixteen element-wise products over the input channels are sixteen GEMMs  M_p[tile, k] = sum_c V_p[tile, c] U_p[c, k]
+// (p = 4 xi + nu, the position inside the 4x4 transformed tile): 2.25x fewer multiplications than the direct form.
+//
+//   winograd_weights_f32   U[p][c][k] = (G g G^T)[xi][nu], formed in fp64 and rounded once; runs once per weight tensor.
+//   conv3x3_winograd_f32   one launch: a workgroup of 4 waves owns 64 tiles x 64 output channels x all 16 positions.
+//       * every wave owns a 32-tile x 32-channel block of ALL sixteen products: 16 accumulators of v_mfma_f32_32x32x2_f32 =
+//         256 registers per lane (one wave per SIMD; the fp32 MFMA reaches its issue rate from one wave with independent
+//         accumulators), so A^T M A happens in registers -- position p of a (tile, channel) sits in the same lane and
+//         register of accumulator p -- and nothing but the result is ever stored;
+//       * the input channels go by in chunks of 8: B^T d B is formed on the way into LDS (each lane transforms two channels
+//         of one tile from 16 8-byte loads), the U slice of the chunk is staged beside it; two LDS buffers, one barrier per
+//         chunk; the next chunk's loads are issued before the current chunk's MFMAs and written behind them;
+//       * dilation d: the convolution is d*d independent undilated ones on the sub-lattices (y mod d, x mod d); a tile is
+//         (image, sub-lattice, tile row, tile column) and its pixels are d apart -- no copies.  Every sub-lattice gets the
+//         tile grid of the largest one; pixels outside the image read as zero and are never stored.
+//   No atomics, no split over the input channels: the result is deterministic.
+#include "common.h"
+#include "../../include/mvdetr_ops.h"
+
+#include <atomic>
+
+namespace mvdetr {
+
+static std::atomic<const char *> g_winograd_last_kernel{"none"};
+static std::atomic<int64_t> g_winograd_launches{0};
+
+namespace wino {
+
+constexpr int TILES = 64;                  // 2x2 output tiles per workgroup
+constexpr int KB = 64;                     // output channels per workgroup
+constexpr int CC = 8;                      // input channels per chunk
+constexpr int VROW = TILES + 4;            // floats per (position, channel) row of V: 68 keeps the four channel pairs that
+                                           // one half-wave writes together on different banks
+constexpr int V_FLOATS = 16 * CC * VROW;   // 8,704
+constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
+constexpr int BUF_FLOATS = V_FLOATS + U_FLOATS;
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TILES * 8;      // two buffers + the tiles' output descriptors = 135,680
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+struct Shape {
+    int N, H, W, C, K, d;
+    int th, tw;                            // tile grid of one sub-lattice
+    unsigned tiles;                        // N * d * d * th * tw
+    int kblocks;                           // K / 64
+};
+
+// Where tile `t` sits: image, top-left OUTPUT pixel (y0, x0); false past the last tile.
+__device__ __forceinline__ bool tile_origin(const Shape &s, unsigned t, int &n, int &y0, int &x0)
+{
+    const bool ok = t < s.tiles;
+    t = ok ? t : 0;
+    const unsigned tx = t % (unsigned)s.tw;
+    unsigned r = t / (unsigned)s.tw;
+    const unsigned ty = r % (unsigned)s.th;
+    r /= (unsigned)s.th;
+    const unsigned dd = (unsigned)(s.d * s.d);
+    const unsigned sub = r % dd;
+    n = (int)(r / dd);
+    y0 = (int)(sub / (unsigned)s.d + 2 * ty * s.d);
+    x0 = (int)(sub % (unsigned)s.d + 2 * tx * s.d);
+    return ok;
+}
+
+typedef __attribute__((address_space(3))) void lds_void;
+typedef const __attribute__((address_space(1))) void global_void;
+
+__global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restrict__ x, const float *__restrict__ U,
+                                                            float *__restrict__ y, const Shape s)
+{
+    // ONE shared array: two {V, U} buffers, then the tiles' output descriptors {pixel offset from the workgroup's first
+    // image, flags}
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int *const tinfo = reinterpret_cast<int *>(lds + 2 * BUF_FLOATS);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // workgroups that share a 64-channel slice of U are 'kblocks' apart: with 8 (or 4, 2, 1) slices, consecutive ids being
+    // dealt round-robin over the 8 XCDs, each XCD's L2 serves one slice
+    const int kb = blockIdx.x % s.kblocks;
+    const unsigned tb = blockIdx.x / s.kblocks;
+    const int C = s.C, K = s.K, d = s.d, H = s.H, W = s.W;
+
+    // every per-lane offset below is 32-bit and relative to the image of the workgroup's first tile (the host bounds the
+    // span of one workgroup's 64 tiles)
+    int n0, uy, ux;
+    tile_origin(s, tb * TILES, n0, uy, ux);
+    const float *const xblk = x + (size_t)n0 * H * W * C;
+    float *const yblk = y + (size_t)n0 * H * W * K + kb * KB;
+
+    // ---- the loader's tile: lane group of 4 = one tile, its 4 channel pairs --------------------------------------------------
+    const int ltile = tid >> 2, cp = tid & 3;
+    int n, y0, x0;
+    const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
+    unsigned mask = 0;                                                        // bit 4 i + j: input pixel (i, j) is in the image
+    unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel pair cp
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int yy = y0 + (i - 1) * d, xx = x0 + (j - 1) * d;
+            const bool ok = tvalid && yy >= 0 && yy < H && xx >= 0 && xx < W;
+            mask |= ok ? 1u << (4 * i + j) : 0u;
+            off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : 0u;
+        }
+    }
+
+    if (tid < TILES) {
+        int tn, ty0, tx0;
+        const bool ok = tile_origin(s, tb * TILES + tid, tn, ty0, tx0);
+        int flags = 0;
+        // a sub-lattice smaller than the largest one has tiles that start outside the image
+        if (ok && ty0 < H && tx0 < W) flags = 1 | (tx0 + d < W ? 2 : 0) | (ty0 + d < H ? 4 : 0);
+        tinfo[2 * tid + 0] = (int)((((unsigned)(tn - n0) * H + ty0) * W + tx0) * (unsigned)K);
+        tinfo[2 * tid + 1] = flags;
+    }
+
+    // ---- U staging by LDS-DMA: the chunk's [16][8][64] slice is 8 x 16 bytes per lane, LDS image in lane order ---------------
+    // float index f = r * 1024 + tid * 4 of the image [p][c][k]:  p = 2 r + (tid >> 7), c = (tid >> 4) & 7, k = (tid & 15) * 4
+    const unsigned uoff = ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + (tid & 15) * 4) * 4u;   // bytes
+    const char *const ublk = reinterpret_cast<const char *>(U + kb * KB);
+    const size_t ustep = (size_t)2 * C * K * 4;                               // two positions further per r, bytes
+
+    float2 raw[16];
+    auto issue_loads = [&](int c0, float *ubuf) {
+        const char *const xc = reinterpret_cast<const char *>(xblk + c0);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) raw[e] = *reinterpret_cast<const float2 *>(xc + off[e]);
+        const char *const uc = ublk + (size_t)c0 * K * 4;
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            __builtin_amdgcn_global_load_lds((global_void *)(uc + r * ustep + uoff), (lds_void *)(ubuf + r * 1024 + wave * 256),
+                                             16, 0, 0);
+    };
+    // rows xi of B^T d B for both channels of the pair -> V[buf][4 xi + nu][2 cp + e][ltile]
+    auto transform_row = [&](float *vbuf, int xi) {
+        const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;                 // t = d[ra] -/+ d[rb]
+        float tx[4], ty[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float2 a = raw[4 * ra + j], b = raw[4 * rb + j];
+            const bool oka = mask >> (4 * ra + j) & 1, okb = mask >> (4 * rb + j) & 1;
+            const float ax = oka ? a.x : 0.f, ay = oka ? a.y : 0.f, bx = okb ? b.x : 0.f, by = okb ? b.y : 0.f;
+            if (xi == 0 || xi == 3) { tx[j] = ax - bx; ty[j] = ay - by; }     // d0 - d2, d1 - d3
+            else if (xi == 1) { tx[j] = ax + bx; ty[j] = ay + by; }           // d1 + d2
+            else { tx[j] = bx - ax; ty[j] = by - ay; }                        // d2 - d1
+        }
+        float *const v0 = vbuf + (4 * xi * CC + 2 * cp) * VROW + ltile;
+        v0[0 * CC * VROW] = tx[0] - tx[2];
+        v0[1 * CC * VROW] = tx[1] + tx[2];
+        v0[2 * CC * VROW] = tx[2] - tx[1];
+        v0[3 * CC * VROW] = tx[1] - tx[3];
+        v0[0 * CC * VROW + VROW] = ty[0] - ty[2];
+        v0[1 * CC * VROW + VROW] = ty[1] + ty[2];
+        v0[2 * CC * VROW + VROW] = ty[2] - ty[1];
+        v0[3 * CC * VROW + VROW] = ty[1] - ty[3];
+    };
+
+    // ---- the wave's block of the sixteen products -----------------------------------------------------------------------------
+    const int wm = wave & 1, wn = wave >> 1;                                  // 32-tile block, 32-channel block
+    const int a_off = (lane >> 5) * VROW + wm * 32 + (lane & 31);             // + (p * CC + 2 s) * VROW
+    const int b_off = V_FLOATS + (lane >> 5) * KB + wn * 32 + (lane & 31);    // + (p * CC + 2 s) * KB
+    f32x16 acc[16];
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+
+    float fa[2][16], fb[2][16];                                               // the operands of two k-steps
+    auto read_step = [&](const float *buf, int st, int set) {
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+            fa[set][p] = buf[a_off + (p * CC + 2 * st) * VROW];
+            fb[set][p] = buf[b_off + (p * CC + 2 * st) * KB];
+        }
+    };
+    auto mfma_step = [&](int set) {
+#pragma unroll
+        for (int p = 0; p < 16; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][p], fb[set][p], acc[p], 0, 0, 0);
+    };
+
+    // prologue: chunk 0 into buffer 0
+    issue_loads(0, lds + V_FLOATS);
+#pragma unroll
+    for (int xi = 0; xi < 4; ++xi) transform_row(lds, xi);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // this wave's LDS-DMA has landed
+    __syncthreads();
+
+    const int chunks = C / CC;
+    for (int ch = 0; ch < chunks; ++ch) {
+        const float *const cur = lds + (ch & 1) * BUF_FLOATS;
+        float *const nxt = lds + ((ch & 1) ^ 1) * BUF_FLOATS;
+        // The next chunk goes into nxt, which was read last before the barrier that ended the previous iteration.  No
+        // branch in the loop: the last iteration stages the last chunk once more, into the buffer nobody reads again.
+        issue_loads((ch + 1 < chunks ? ch + 1 : ch) * CC, nxt + V_FLOATS);
+        read_step(cur, 0, 0);
+        read_step(cur, 1, 1);
+        mfma_step(0);
+        mfma_step(1);
+        // nothing of the transform moves above this line: its first instruction waits for the loads, which get the two
+        // steps above (2,048 cycles of MFMA) to land; and the last two steps' operands are read before V's writes, which
+        // the compiler cannot tell from them
+        __builtin_amdgcn_sched_barrier(0);
+        read_step(cur, 2, 0);
+        read_step(cur, 3, 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int xi = 0; xi < 4; ++xi) transform_row(nxt, xi);
+        mfma_step(0);
+        mfma_step(1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    // ---- A^T M A in registers, then the stores ------------------------------------------------------------------------------------
+    const int kcol = wn * 32 + (lane & 31);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);     // the accumulator's row = the tile
+        const int flags = tinfo[2 * t + 1];
+        const unsigned pix = (unsigned)tinfo[2 * t + 0];
+        float s0[4], s1[4];
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            s0[nu] = acc[nu][r] + acc[4 + nu][r] + acc[8 + nu][r];
+            s1[nu] = acc[4 + nu][r] - acc[8 + nu][r] - acc[12 + nu][r];
+        }
+        const float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+        const float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+        float *const o = yblk + pix + kcol;
+        if (flags & 1) {
+            o[0] = y00;
+            if (flags & 2) o[(size_t)d * K] = y01;
+            if (flags & 4) {
+                o[(size_t)d * W * K] = y10;
+                if (flags & 2) o[(size_t)d * W * K + (size_t)d * K] = y11;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);                                    // one register's sixteen reads at a time
+    }
+}
+
+// U[p = 4 xi + nu][c][k] = (G g G^T)[xi][nu] of weight[k][c][3][3], in fp64, rounded once.  One thread per (c, k).
+__global__ __launch_bounds__(256) void winograd_weights_f32(const float *__restrict__ w, int C, int K, float *__restrict__ U)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)C * K) return;
+    const int k = (int)(i % K), c = (int)(i / K);
+    const float *g = w + ((size_t)k * C + c) * 9;
+    double t[4][3];                                                           // G g
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double g0 = g[j], g1 = g[3 + j], g2 = g[6 + j];
+        t[0][j] = g0;
+        t[1][j] = 0.5 * (g0 + g1 + g2);
+        t[2][j] = 0.5 * (g0 - g1 + g2);
+        t[3][j] = g2;
+    }
+#pragma unroll
+    for (int xi = 0; xi < 4; ++xi) {
+        const double u[4] = {t[xi][0], 0.5 * (t[xi][0] + t[xi][1] + t[xi][2]), 0.5 * (t[xi][0] - t[xi][1] + t[xi][2]), t[xi][2]};
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) U[((size_t)(4 * xi + nu) * C + c) * K + k] = (float)u[nu];
+    }
+}
+
+static PerDevice<int> g_lds_attr;
+
+}  // namespace wino
+}  // namespace mvdetr
+
+extern "C" int mvdetr_winograd_weights_f32(const float *w, int C, int K, float *U, void *stream)
+{
+    using namespace mvdetr;
+    if (!w || !U || C <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    if (C % 8 != 0 || K % 64 != 0 || !aligned(w, 4) || !aligned(U, 16) || (int64_t)C * K > (int64_t)1 << 26)
+        return (int)hipErrorNotSupported;
+    hipLaunchKernelGGL(wino::winograd_weights_f32, dim3((unsigned)(((int64_t)C * K + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), w, C, K, U);
+    g_winograd_last_kernel = "winograd_weights_f32";
+    g_winograd_launches.fetch_add(1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mvdetr_conv3x3_winograd_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K,
+                                           int dilation, void *stream)
+{
+    using namespace mvdetr;
+    if (!x || !U || !y || x == y || N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    if (C % 8 != 0 || K % 64 != 0 || !(dilation == 1 || dilation == 2 || dilation == 4) || !aligned(x, 16) ||
+        !aligned(U, 16) || !aligned(y, 16))
+        return (int)hipErrorNotSupported;
+    // a lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
+    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one)
+    if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
+    if (N == 0) return 0;
+    wino::Shape s;
+    s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
+    s.th = ((H + dilation - 1) / dilation + 1) / 2;
+    s.tw = ((W + dilation - 1) / dilation + 1) / 2;
+    const int64_t tiles = (int64_t)N * dilation * dilation * s.th * s.tw;
+    s.kblocks = K / wino::KB;
+    const int64_t blocks = (tiles + wino::TILES - 1) / wino::TILES * s.kblocks;
+    if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
+    s.tiles = (unsigned)tiles;
+    const int rc = wino::g_lds_attr.get([] {
+        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(wino::conv3x3_winograd_f32),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, wino::LDS_BYTES);
+    });
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(wino::conv3x3_winograd_f32, dim3((unsigned)blocks), dim3(256), wino::LDS_BYTES,
+                       reinterpret_cast<hipStream_t>(stream), x, U, y, s);
+    g_winograd_last_kernel = "conv3x3_winograd_f32";
+    g_winograd_launches.fetch_add(1);
+    return (int)hipGetLastError();
+}
+
+extern "C" const char *mvdetr_winograd_last_kernel(void) { return mvdetr::g_winograd_last_kernel.load(); }
+
+extern "C" int64_t mvdetr_winograd_launch_count(void) { return mvdetr::g_winograd_launches.load(); }

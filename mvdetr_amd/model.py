@@ -1,7 +1,8 @@
 """Minimal caller of the fusion path: an MVDeTr-shaped detector whose warp and deformable attention
 run on the HIP kernels.  The trunk's and the heads' convolutions are ordinary PyTorch-ROCm, as in the
 reference; in inference the trunk's BatchNorm / ReLU / residual-add / max-pool passes between them run
-fused on HIP kernels (ops/trunk_epilogue.py), and as the modules' own torch ops everywhere else.
+fused on HIP kernels (ops/trunk_epilogue.py), and as the modules' own torch ops everywhere else; the wide 3x3
+convolutions of layer3/4 that measured faster that way run as an fp32 Winograd MFMA kernel (ops/conv_winograd.py).
 
 Mirrors multiview_detector/models/mvdetr.py:74-218 (constructor arithmetic, forward order, output
 tuple) and the dilated ResNet-18 trunk of multiview_detector/models/resnet.py:33-70,120-186
@@ -18,6 +19,7 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
+from .ops.conv_winograd import winograd_conv3x3, winograd_conv3x3_available
 from .ops.detect import bev_detect
 from .ops.ingest import ingest_frames
 from .ops.trunk_epilogue import (bn_act, bn_act_half, bn_relu_maxpool, bn_relu_maxpool_half, fused_bn_act_available,
@@ -34,6 +36,14 @@ def _fused_bn_act(out, bn, residual=None, residual_bn=None):
     if fused_bn_act_half_available(out, bn, residual, residual_bn):
         return bn_act_half
     return None
+
+
+def _conv3x3(x, conv):
+    """conv(x): the fp32 Winograd kernel where it takes these arguments (inference, wide 3x3 convolutions at the trunk's
+    size), torch's convolution otherwise."""
+    if winograd_conv3x3_available(x, conv):
+        return winograd_conv3x3(x, conv)
+    return conv(x)
 
 
 def _bn_relu(out, bn, relu):
@@ -101,8 +111,8 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        out = _bn_relu(self.conv1(x), self.bn1, self.relu)
-        return _bn_add_relu(self.conv2(out), self.bn2, x, self.downsample, self.relu)
+        out = _bn_relu(_conv3x3(x, self.conv1), self.bn1, self.relu)
+        return _bn_add_relu(_conv3x3(out, self.conv2), self.bn2, x, self.downsample, self.relu)
 
 
 class Bottleneck(nn.Module):
@@ -124,7 +134,7 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         out = _bn_relu(self.conv1(x), self.bn1, self.relu)
-        out = _bn_relu(self.conv2(out), self.bn2, self.relu)
+        out = _bn_relu(_conv3x3(out, self.conv2), self.bn2, self.relu)
         return _bn_add_relu(self.conv3(out), self.bn3, x, self.downsample, self.relu)
 
 

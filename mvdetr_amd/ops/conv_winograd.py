@@ -1,0 +1,159 @@
+"""The trunk's wide 3x3 convolutions as an fp32 Winograd F(2x2, 3x3) MFMA kernel (csrc/conv_winograd.hip): 2.25x fewer
+multiplications than the direct form, fp32 inputs, products and sums throughout.  Inference only, channel-last fp32 CUDA
+activations, stride 1, padding = dilation in {1, 2, 4}, no bias, and only the (C, K, dilation) families that measured
+faster than MIOpen's pick; everything else keeps torch's convolution: the callers in model.py ask the
+predicate first.
+
+The transformed weights U = G g G^T (fp64, rounded once) are built once per weight tensor and cached."""
+from __future__ import annotations
+
+import os
+import weakref
+
+import torch
+from torch import nn
+
+from .. import _lib
+
+_enabled = os.environ.get("MVDETR_TRUNK_WINOGRAD", "1") != "0"
+
+# F(2x2, 3x3):  Y = A^T [ (G g G^T) .* (B^T d B) ] A.  The kernels hard-code these (winograd_weights_f32 forms G g G^T,
+# the convolution's loader B^T d B and its epilogue A^T M A); tests/test_conv_winograd.py pins them against a direct form.
+G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+BT = ((1.0, 0.0, -1.0, 0.0), (0.0, 1.0, 1.0, 0.0), (0.0, -1.0, 1.0, 0.0), (0.0, 1.0, 0.0, -1.0))
+AT = ((1.0, 1.0, 1.0, 0.0), (0.0, 1.0, -1.0, -1.0))
+
+# (C, K) -> dilations switched on: the shapes on which the kernel beat MIOpen's pick in every repetition of
+# tools/conv_bench.py at the trunk's size (profiles/trunk_winograd_shapes.txt)
+FAMILIES: dict = {(128, 256): (1,), (256, 256): (1, 2), (256, 512): (2,), (512, 512): (1, 4)}
+DILATIONS = (1, 2, 4)
+
+# Below this many output pixels (N * H * W) torch's convolution stays: 8,192 pixels = 32 blocks of 64 tiles x 8 blocks of
+# 64 channels = one workgroup per CU at K = 512.
+MIN_PIXELS = 8192
+_min_pixels = MIN_PIXELS
+
+
+def set_trunk_winograd(on: bool) -> bool:
+    """Switch the Winograd convolutions on or off for this process (default on; ``MVDETR_TRUNK_WINOGRAD=0`` starts with
+    them off).  Returns the previous setting.  Independent of ``set_trunk_fusion``."""
+    global _enabled
+    prev, _enabled = _enabled, bool(on)
+    return prev
+
+
+def trunk_winograd_enabled() -> bool:
+    return _enabled
+
+
+def set_winograd_min_pixels(pixels: int) -> int:
+    """The pixel floor of winograd_conv3x3_available() (MIN_PIXELS by default); returns the previous one.  For tests, which
+    run the model on small images."""
+    global _min_pixels
+    prev, _min_pixels = _min_pixels, int(pixels)
+    return prev
+
+
+def last_kernel() -> str:
+    """Name of the kernel the last Winograd call of this process launched ("none" before the first)."""
+    return _lib.lib().mvdetr_winograd_last_kernel().decode()
+
+
+def launch_count() -> int:
+    """Number of Winograd launches (weight transforms included) of this process so far."""
+    return int(_lib.lib().mvdetr_winograd_launch_count())
+
+
+def _on_device(t) -> bool:
+    return t.is_cuda
+
+
+def _two(v, want) -> bool:
+    return v == want or tuple(v) == (want, want)
+
+
+def _structure_ok(x, conv) -> bool:
+    """What the kernel itself needs, whatever the switches say."""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.dtype == torch.float32 and _on_device(x) and x.numel() > 0
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    if type(conv) is not nn.Conv2d:
+        return False
+    d = conv.dilation[0]
+    if not (_two(conv.kernel_size, 3) and _two(conv.stride, 1) and conv.groups == 1 and conv.bias is None
+            and conv.padding_mode == "zeros" and d in DILATIONS and _two(conv.dilation, d)
+            and not isinstance(conv.padding, str) and _two(conv.padding, d)):
+        return False
+    w = conv.weight
+    C, K = conv.in_channels, conv.out_channels
+    if not (w.dtype == torch.float32 and w.device == x.device and x.shape[1] == C and C % 8 == 0 and K % 64 == 0):
+        return False
+    if (256 + 2 * x.shape[2] * x.shape[3]) * max(C, K) >= 1 << 30:
+        return False
+    # nothing that needs autograd: the kernel is forward only
+    return not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))
+
+
+def winograd_conv3x3_available(x: torch.Tensor, conv: nn.Module) -> bool:
+    """True when the model runs ``conv`` on ``x`` through the Winograd kernel: the switch is on, CUDA fp32 dense
+    channel-last x, a plain nn.Conv2d with a 3x3 kernel, stride 1, groups 1, padding == dilation in {1, 2, 4}, no bias,
+    zero padding, (C, K, dilation) in a family that measured faster than MIOpen, nothing that needs autograd,
+    ``torch.backends.cudnn.deterministic`` off (a caller who asked for the library's deterministic solvers keeps torch's
+    convolution) and at least the pixel floor of output pixels."""
+    if not (_enabled and _structure_ok(x, conv)) or torch.backends.cudnn.deterministic:
+        return False
+    if conv.dilation[0] not in FAMILIES.get((conv.in_channels, conv.out_channels), ()):
+        return False
+    return x.shape[0] * x.shape[2] * x.shape[3] >= _min_pixels
+
+
+class _Entry:
+    __slots__ = ("ref", "alias", "version", "U")
+
+
+_cache: dict = {}
+
+
+def _transformed_weights(weight: torch.Tensor) -> torch.Tensor:
+    """U [16, C, K] of this weight tensor, built on first use and again whenever the tensor was written in place
+    (``_version``: ``weight.copy_``, ``load_state_dict``) or given new storage (``.to()``).  One entry per tensor OBJECT, found
+    by its id and confirmed through a weak reference; the entry holds an alias of the storage it was built from, so that
+    address cannot be handed out again while the entry lives, and goes away with the tensor."""
+    key = id(weight)
+    e = _cache.get(key)
+    if (e is not None and e.ref() is weight and e.alias.data_ptr() == weight.data_ptr() and e.version == weight._version
+            and e.alias.device == weight.device and e.alias.stride() == weight.stride()):
+        return e.U
+    K, C = weight.shape[0], weight.shape[1]
+    w = weight.detach()
+    dense = w.contiguous()                                                    # [K, C, 3, 3] OIHW memory
+    U = torch.empty((16, C, K), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        code = _lib.lib().mvdetr_winograd_weights_f32(dense.data_ptr(), C, K, U.data_ptr(), _lib.current_stream_ptr(w.device))
+    _lib.check(code, "winograd_weights")
+    e = _Entry()
+    e.ref = weakref.ref(weight, lambda _, key=key: _cache.pop(key, None))
+    e.alias, e.version, e.U = w, weight._version, U
+    _cache[key] = e
+    return U
+
+
+def cached_weight_count() -> int:
+    return len(_cache)
+
+
+def winograd_conv3x3(x: torch.Tensor, conv: nn.Conv2d, force: bool = False) -> torch.Tensor:
+    """``conv(x)`` by the Winograd kernel: a fresh channel-last tensor.  ``force`` skips the switch, the family table, the
+    pixel floor and the cudnn.deterministic rule (tests and tools: any shape the kernel itself takes).  Raises when the
+    arguments do not take the kernel: callers decide, nothing falls back silently here."""
+    if not (_structure_ok(x, conv) if force else winograd_conv3x3_available(x, conv)):
+        raise RuntimeError("winograd_conv3x3: these arguments do not take the kernel (see winograd_conv3x3_available)")
+    U = _transformed_weights(conv.weight)
+    N, C, H, W = x.shape
+    K = conv.out_channels
+    y = torch.empty((N, K, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    with torch.cuda.device(x.device):
+        code = _lib.lib().mvdetr_conv3x3_winograd_f32(x.data_ptr(), U.data_ptr(), y.data_ptr(), N, H, W, C, K,
+                                                      conv.dilation[0], _lib.current_stream_ptr(x.device))
+    _lib.check(code, "conv3x3_winograd")
+    return y

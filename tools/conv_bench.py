@@ -1,0 +1,83 @@
+"""The trunk's eight layer3/4 3x3 convolutions at Wildtrack size (7 x 90 x 160 pixels, fp32, channel-last): torch's
+convolution (cudnn.benchmark = True, as bench.py sets: MIOpen picks by measurement) against the Winograd F(2x2,3x3)
+MFMA kernel, interleaved in one process, HIP events.
+
+    python tools/conv_bench.py [--reps 5] [--launches 20] [--out profiles/trunk_winograd_shapes.txt]
+
+A repetition times `launches` back-to-back launches of one side, then of the other; a family is switched on in
+mvdetr_amd/ops/conv_winograd.py only where the kernel is faster in EVERY repetition.  Also prints each shape's deviation
+from an fp64 convolution for both sides (max-abs, on a post-ReLU N(0,1) input and kaiming weights)."""
+import argparse
+import os
+import sys
+
+import torch
+from torch import nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = [  # name, C, K, dilation
+    ("layer3.0.conv1", 128, 256, 1), ("layer3.x.conv2", 256, 256, 1), ("layer3.1.conv1", 256, 256, 2),
+    ("layer4.0.conv1", 256, 512, 2), ("layer4.x.conv2", 512, 512, 1), ("layer4.1.conv1", 512, 512, 4),
+]
+
+
+def timed(fn, launches):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / launches
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--pixels", type=int, nargs=3, default=(7, 90, 160), metavar=("N", "H", "W"))
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    from mvdetr_amd.ops import conv_winograd as cw
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device("cuda:0")
+    N, H, W = args.pixels
+    lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, {N} x {H} x {W} pixels, fp32 channel-last, ms per launch "
+             f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",
+             "# shape               C->K     d  GFLOP   torch min/med/max        winograd min/med/max     TF/s(direct-equivalent)  "
+             "wins  err torch / winograd vs fp64"]
+    for name, C, K, d in SHAPES:
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last).eval()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        with torch.no_grad():
+            for _ in range(3):
+                ref32, got = conv(x), cw.winograd_conv3x3(x, conv, force=True)
+            sub = slice(0, 1)
+            want = nn.functional.conv2d(x[sub].double(), conv.weight.double(), None, 1, d, d)
+            e_t, e_w = (ref32[sub] - want).abs().max().item(), (got[sub] - want).abs().max().item()
+            t_t, t_w = [], []
+            for _ in range(args.reps):
+                t_t.append(timed(lambda: conv(x), args.launches))
+                t_w.append(timed(lambda: cw.winograd_conv3x3(x, conv, force=True), args.launches))
+        gflop = 2.0 * N * H * W * C * K * 9 / 1e9
+        wins = sum(w < t for w, t in zip(t_w, t_t))
+        med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+        lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {gflop:6.1f}  {min(t_t):6.3f} {med(t_t):6.3f} {max(t_t):6.3f}     "
+                     f"{min(t_w):6.3f} {med(t_w):6.3f} {max(t_w):6.3f}     {gflop / med(t_w):7.1f}                  {wins}/{args.reps}   "
+                     f"{e_t:.2e} / {e_w:.2e}")
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+    else:
+        print(text)
+
+
+if __name__ == "__main__":
+    main()

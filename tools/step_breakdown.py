@@ -19,7 +19,9 @@ GROUPS = ("convolutions (MIOpen / CK)", "elementwise passes", "this library", "G
 
 def group_of(name):
     if "mvdetr::" in name:
-        # the trunk's fused passes are elementwise work moved into this library: counted with what they replace
+        # the trunk's fused passes and its Winograd convolutions are work moved into this library: counted with what they replace
+        if re.search(r"conv3x3_winograd", name):
+            return GROUPS[0]
         return GROUPS[1] if re.search(r"bn_act_cl|bn_relu_maxpool", name) else GROUPS[2]
     if re.search(r"BatchNorm|elementwise_kernel|max_pool|batched_transpose|SubTensorOp|direct_copy|copy_kernel|CatArrayBatchedCopy|"
                  r"upsample|index_elementwise|reduce_kernel|FillFunctor|transpose_kernel", name):
