@@ -1,6 +1,7 @@
 """CPU-only checks of the Winograd convolution's Python face (mvdetr_amd/ops/conv_winograd.py): the predicate's truth
-table, the transformed-weights cache, and the F(2x2,3x3) matrices.  No kernel is launched: the predicate is asked about
-meta tensors standing in for device ones, and the cache is exercised with the weight transform's launch replaced by a
+table, the transformed-weights cache, the F(2x2,3x3) matrices, and the oracle of the GPU tests (conv_winograd_oracle.py: the
+float32 emulation at every geometry, exact on integer data).  No kernel is launched: the predicate is asked about meta
+tensors standing in for device ones, and the cache is exercised with the weight transform's launch replaced by a
 counter."""
 import copy
 
@@ -9,6 +10,7 @@ import pytest
 import torch
 from torch import nn
 
+import conv_winograd_oracle as oracle
 from mvdetr_amd.ops import conv_winograd as cw
 
 
@@ -195,3 +197,59 @@ def test_float32_f2x2_3x3_is_within_a_few_ulp_of_fp64():
             got[:, 2 * ty:2 * ty + 2, 2 * tx:2 * tx + 2] = np.einsum("ij,kjl,ml->kim", AT, M, AT)
     err = np.abs(got - want).max()
     assert np.abs(want).max() > 1 and err < 16 * np.spacing(np.float32(np.abs(want).max()))
+
+
+# ---- the oracle of the GPU tests (tests/conv_winograd_oracle.py), validated without a GPU ------------------------------------------
+
+def test_oracle_weights_have_the_kernels_layout():
+    w = torch.randn(64, 8, 3, 3, generator=torch.Generator().manual_seed(2))
+    assert np.array_equal(oracle.transformed_weights(w.numpy()), _numpy_weights(w))
+
+
+@pytest.mark.parametrize("N,C,K,H,W,d", [(3, 24, 64, 5, 7, 4), (3, 24, 64, 9, 13, 2), (3, 8, 64, 3, 2, 4), (3, 256, 64, 10, 16, 1),
+                                         (3, 8, 64, 2, 2, 1), (3, 24, 64, 6, 4, 1), (2, 72, 64, 1, 9, 2)])
+def test_generalised_emulation_is_exact_on_integer_cases(N, C, K, H, W, d):
+    """Integer activations in [-3, 3], weights 4 * [-2, 2]: every intermediate of float32 F(2x2,3x3) is an integer below 2^24
+    (integer_case asserts the bound), so the emulation equals the fp64 direct convolution bit for bit -- dilated, odd, smaller
+    than the dilation."""
+    x, w = oracle.integer_case(N, C, K, H, W, d)
+    assert x.is_contiguous(memory_format=torch.channels_last) and x.min() == -3 and x.max() == 3
+    assert set(w.unique().tolist()) == {-8.0, -4.0, 0.0, 4.0, 8.0}
+    want = oracle.direct_fp64(x, w, d)
+    got = torch.from_numpy(oracle.emulate_f32(x.numpy(), w.numpy(), d))
+    oracle.check_sanity(want, C)
+    assert torch.equal(got.double(), want), oracle.first_mismatch(got, want, d)
+
+
+@pytest.mark.parametrize("H,W,d", [(10, 16, 1), (5, 7, 1), (9, 13, 2), (5, 7, 4), (3, 2, 4), (18, 17, 2)])
+def test_generalised_emulation_on_random_data_is_within_a_few_ulp_of_fp64(H, W, d):
+    """Kaiming weights, post-ReLU N(0,1) activations as in the trunk: the bar of
+    test_float32_f2x2_3x3_is_within_a_few_ulp_of_fp64."""
+    g = torch.Generator().manual_seed(17 * H + W + 101 * d)
+    C, K = 64, 64
+    w = torch.randn(K, C, 3, 3, generator=g) * (2.0 / (K * 9)) ** 0.5
+    x = torch.randn(2, C, H, W, generator=g).relu_()
+    want = oracle.direct_fp64(x, w, d).numpy()
+    got = oracle.emulate_f32(x.numpy(), w.numpy(), d)
+    err = np.abs(got - want).max()
+    assert np.abs(want).max() > 1 and err < 16 * np.spacing(np.float32(np.abs(want).max()))
+    assert err > 0                                                             # (float32 arithmetic, not fp64 in disguise)
+
+
+def test_every_exact_case_has_a_reference_worth_comparing_with():
+    """The sanity condition of tests/test_conv_winograd_exact_gpu.py on its three grids: at least 90 % of the reference outputs
+    non-zero, max |want| > 50 from C = 24 on."""
+    assert len(oracle.GEOMETRY_GRID) == 108 and len(oracle.CHANNEL_GRID) == 54 and len(oracle.BOUNDARY_GRID) == 9
+    for N, C, K, H, W, d in oracle.GEOMETRY_GRID + oracle.CHANNEL_GRID + oracle.BOUNDARY_GRID:
+        x, w = oracle.integer_case(N, C, K, H, W, d)
+        oracle.check_sanity(oracle.direct_fp64(x, w, d), C)
+
+
+def test_the_span_guard_of_the_predicate(on_device):
+    """(256 + 2 H W) * max(C, K) < 2^30: the last shape below the limit takes the kernel, the first above does not (the C entry's
+    own guard is in tests/test_conv_winograd_gpu.py; nothing this large is ever launched)."""
+    with torch.no_grad():
+        for C, K, H, W, W_over in ((64, 64, 2896, 2896, 2897), (128, 64, 2048, 2047, 2048), (64, 128, 2048, 2047, 2048)):
+            assert (256 + 2 * H * W) * max(C, K) < 1 << 30 <= (256 + 2 * H * W_over) * max(C, K)
+            assert cw._structure_ok(_x(C, H, W), _conv(C, K))
+            assert not cw._structure_ok(_x(C, H, W_over), _conv(C, K))
