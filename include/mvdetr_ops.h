@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 17   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again) */
+#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -313,6 +313,11 @@ int mvdetr_add_layernorm_add_f16(void *stream, const uint16_t *x, const uint16_t
 int mvdetr_add_layernorm_add_bf16(void *stream, const uint16_t *x, const uint16_t *residual, const uint16_t *weight,
                                   const uint16_t *bias, const uint16_t *add2, int64_t add2_rows, int64_t rows, int cols,
                                   float eps, uint16_t *out, uint16_t *out2);
+/* Name of the kernel the last add + LayerNorm call of this process launched: the kernels' own names,
+ * "add_layernorm_rows128x2" (128 columns, every pointer 16-byte aligned), "add_layernorm_rows<1>" / "<2>" / "<4>" (64 / 128 / 256
+ * columns, one row per wave), "add_layernorm_rows_half<COLS,VEC>" (VEC = 8: 16-byte aligned; VEC = COLS / 64 otherwise);
+ * "none" before the first launch.  A refused call (801, 1) leaves it unchanged.  Host-side static storage; never NULL. */
+const char *mvdetr_add_layernorm_last_kernel(void);
 
 /* ---- The ResNet trunk's inference epilogues (csrc/trunk_epilogue.hip) ---------------------------
  * Eval-mode BatchNorm2d with what follows it in a residual block, one pass over channel-last fp32 activations:

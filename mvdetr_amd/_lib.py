@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # MVDETR_OPS_LIB: another build of the same sources (the phase-stamp build libmvdetr_ops_trace.so of tools/experiments)
 LIB_PATH = os.environ.get("MVDETR_OPS_LIB") or os.path.join(CSRC, "libmvdetr_ops.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _vp, _i = ctypes.c_void_p, ctypes.c_int
 _MSDA_FWD = [_vp] * 6 + [_i] * 7 + [_vp]
@@ -89,6 +89,7 @@ SIGNATURES = {
     "mvdetr_add_layernorm_add_f32": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
     "mvdetr_add_layernorm_add_f16": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
     "mvdetr_add_layernorm_add_bf16": ([_vp] * 6 + [ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_float, _vp, _vp], _i),
+    "mvdetr_add_layernorm_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_bn_act_f32": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),
     "mvdetr_bn_relu_maxpool_f32": ([_vp] * 6 + [ctypes.c_float] + [_i] * 4 + [_vp], _i),
     "mvdetr_bn_act_f16": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float, ctypes.c_int64, _i, _i, _vp], _i),

@@ -11,7 +11,11 @@
 #include "half_types.h"
 #include "../../include/mvdetr_ops.h"
 
+#include <atomic>
+
 namespace mvdetr {
+
+static std::atomic<const char *> g_add_layernorm_last_kernel{"none"};
 
 template <int VEC>
 __global__ __launch_bounds__(256) void add_layernorm_rows(const float *__restrict__ x, const float *__restrict__ res,
@@ -198,6 +202,8 @@ static int add_layernorm_half_launch(hipStream_t st, bool a16, const uint16_t *x
     const int rpw = a16 ? 512 / COLS : 1;
     const int64_t want = (rows + 4 * rpw - 1) / (4 * rpw);                           // four waves per block
     const unsigned blocks = (unsigned)(want < 256 * 16 ? want : 256 * 16);          // grid-stride above 16 blocks per CU
+    g_add_layernorm_last_kernel = a16 ? (COLS == 64 ? "add_layernorm_rows_half<64,8>" : COLS == 128 ? "add_layernorm_rows_half<128,8>" : "add_layernorm_rows_half<256,8>")
+                                      : (COLS == 64 ? "add_layernorm_rows_half<64,1>" : COLS == 128 ? "add_layernorm_rows_half<128,2>" : "add_layernorm_rows_half<256,4>");
     if (a16) hipLaunchKernelGGL((add_layernorm_rows_half<C, COLS, 8>), dim3(blocks), dim3(256), 0, st, x, res, gamma, beta, add2, add2_rows, rows, eps, out, out2);
     else hipLaunchKernelGGL((add_layernorm_rows_half<C, COLS, COLS / 64>), dim3(blocks), dim3(256), 0, st, x, res, gamma, beta, add2, add2_rows, rows, eps, out, out2);
     return (int)hipGetLastError();
@@ -227,6 +233,8 @@ static int add_layernorm_half_entry(void *stream, const uint16_t *x, const uint1
 
 }  // namespace mvdetr
 
+extern "C" const char *mvdetr_add_layernorm_last_kernel(void) { return mvdetr::g_add_layernorm_last_kernel.load(); }
+
 extern "C" int mvdetr_add_layernorm_f32(void *stream, const float *x, const float *residual, const float *weight,
                                         const float *bias, int64_t rows, int cols, float eps, float *out)
 {
@@ -255,9 +263,11 @@ extern "C" int mvdetr_add_layernorm_add_f32(void *stream, const float *x, const 
     if (cols == 128 && a16) {
         const int64_t want2 = (rows + 7) / 8;                                          // two rows per wave, four waves per block
         const unsigned blocks2 = (unsigned)(want2 < 256 * 16 ? want2 : 256 * 16);
+        g_add_layernorm_last_kernel = "add_layernorm_rows128x2";
         hipLaunchKernelGGL(add_layernorm_rows128x2, dim3(blocks2), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
         return (int)hipGetLastError();
     }
+    g_add_layernorm_last_kernel = cols == 64 ? "add_layernorm_rows<1>" : cols == 128 ? "add_layernorm_rows<2>" : "add_layernorm_rows<4>";
     if (cols == 64) hipLaunchKernelGGL(add_layernorm_rows<1>, dim3(blocks), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
     else if (cols == 128) hipLaunchKernelGGL(add_layernorm_rows<2>, dim3(blocks), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);
     else hipLaunchKernelGGL(add_layernorm_rows<4>, dim3(blocks), dim3(256), 0, st, x, residual, weight, bias, add2, add2_rows, rows, eps, out, out2);

@@ -461,7 +461,7 @@ def test_mini_trans_model_runs_a_frame_and_trains_on_the_cpu():
 
 def test_abi_version_and_symbols():
     from mvdetr_amd import _lib
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mvdetr_ops_abi_version() == 17
+    assert _lib.ABI_VERSION == 18 and _lib.lib().mvdetr_ops_abi_version() == 18
     assert _lib.lib().mvdetr_attention_workspace_bytes(2, 8, 100, 50, 16, 4) == 2 * 8 * 100 * 4
     names = [n for n in _lib.SIGNATURES if "attention" in n]
     assert len(names) == 11 and np.all([hasattr(_lib.lib(), n) for n in names])

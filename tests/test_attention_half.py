@@ -105,7 +105,7 @@ def test_new_symbols_are_declared_bound_and_exported_and_the_abi_version_stays()
     lib = _lib.lib()
     for name in ("mvdetr_attn_forward_f16", "mvdetr_attn_forward_bf16", "mvdetr_attn_half_set_query_tile"):
         assert re.search(rf"\b{name}\(", hdr) and name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 17 and lib.mvdetr_ops_abi_version() == 17
+    assert _lib.ABI_VERSION == 18 and lib.mvdetr_ops_abi_version() == 18
     # the entries validate before they touch the device: no GPU is needed to be refused
     strides = (ctypes.c_int64 * 12)()
     assert lib.mvdetr_attn_forward_bf16(None, None, None, None, strides, 1, 1, 4, 4, 20, None) == 801

@@ -208,8 +208,8 @@ def _saved(tmp_path, rows):
 def test_new_symbols_are_declared_and_the_abi_version_stays():
     names = ["mvdetr_detect_workspace_bytes", "mvdetr_detect_last_kernel", "mvdetr_detect_launch_count"]
     names += [f"mvdetr_{op}{host}_{t}" for op in ("detect_forward", "distance_nms") for host in ("", "_host") for t in ("f32", "f64")]
-    assert set(names) <= set(_lib.SIGNATURES) and _lib.ABI_VERSION == 17
+    assert set(names) <= set(_lib.SIGNATURES) and _lib.ABI_VERSION == 18
     lib = _lib.lib()
-    assert lib.mvdetr_ops_abi_version() == 17
+    assert lib.mvdetr_ops_abi_version() == 18
     assert lib.mvdetr_detect_workspace_bytes(1, 120, 360, 4) > 0 and lib.mvdetr_detect_workspace_bytes(1, 0, 360, 4) < 0
     assert lib.mvdetr_detect_workspace_bytes(1, 120, 360, 2) < 0

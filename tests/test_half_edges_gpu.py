@@ -333,7 +333,7 @@ def test_add_layer_norm_half_without_16_byte_alignment(dtype, cols, with_res, wi
     """add_layernorm_rows_half<COLS, COLS / 64> (one row per wave): every input starts cols / 64 elements into its buffer --
     the C entry's minimum alignment, a lane's cols / 64 elements as one access, but not 16 bytes.  The reduction order is not
     the aligned instantiation's, so the comparison is with the oracle."""
-    from mvdetr_amd.ops.add_layernorm import add_layer_norm, fused_add_layer_norm_available
+    from mvdetr_amd.ops.add_layernorm import add_layer_norm, fused_add_layer_norm_available, last_kernel
     x, res, pos, norm = ln_inputs(2, 37, cols, dtype, with_res, with_add, 37 + cols)
     xo, ro, po = (at_offset(t, cols // 64) for t in (x, res, pos))
     for t in (xo, ro, po):                                                    # the condition that selects the instantiation
@@ -341,6 +341,7 @@ def test_add_layer_norm_half_without_16_byte_alignment(dtype, cols, with_res, wi
     with torch.no_grad():
         assert fused_add_layer_norm_available(xo, norm)
         got = add_layer_norm(xo, ro, norm, then_add=po)
+    assert last_kernel() == f"add_layernorm_rows_half<{cols},{cols // 64}>"
     check_ln(got, ln_oracle(x, res, norm), pos, dtype)
 
 
@@ -378,17 +379,19 @@ def test_add_layer_norm_half_below_the_minimum_alignment_runs_torch_ops(dtype, c
 def test_add_layer_norm_half_grid_stride(dtype, cols):
     """More rows than 4096 workgroups hold (4 waves of 512 / cols rows each): the grid-stride loop of the aligned instantiation,
     and -- the same rows at an offset of cols / 64 elements, one row per wave -- of the unaligned one."""
-    from mvdetr_amd.ops.add_layernorm import add_layer_norm
+    from mvdetr_amd.ops.add_layernorm import add_layer_norm, last_kernel
     rows = 4096 * 4 * (512 // cols) + 37
     assert -(-rows // (4 * (512 // cols))) > 4096 and -(-rows // 4) > 4096     # the launcher's block counts, both instantiations
     x, res, pos, norm = ln_inputs(1, rows, cols, dtype, True, True, 43 + cols)
     want = ln_oracle(x, res, norm)
     with torch.no_grad():
         aligned = add_layer_norm(x.cuda(), res.cuda(), norm, then_add=pos.cuda())
+        assert last_kernel() == f"add_layernorm_rows_half<{cols},8>"
         check_ln(aligned, want, pos, dtype)
         del aligned
         check_ln(add_layer_norm(*(at_offset(t, cols // 64) for t in (x, res)), norm, then_add=at_offset(pos, cols // 64)),
                  want, pos, dtype)
+        assert last_kernel() == f"add_layernorm_rows_half<{cols},{cols // 64}>"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

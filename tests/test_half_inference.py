@@ -24,8 +24,8 @@ def test_new_symbols_are_declared_and_bound_and_the_abi_version_stays():
     for name in NEW_SYMBOLS:
         assert name in declared, name
         assert name in _lib.SIGNATURES, name
-    assert _lib.ABI_VERSION == 17
-    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 17\b", hdr)
+    assert _lib.ABI_VERSION == 18
+    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 18\b", hdr)
     # 16-bit tensors cross the ABI as uint16_t *, the warp's matrices and the reference points stay float
     for name in NEW_SYMBOLS:
         if name.endswith("_supported"):

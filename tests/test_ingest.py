@@ -176,8 +176,8 @@ def test_symbols_are_declared_bound_and_exported():
     exported = set(re.findall(r" T (mvdetr_[a-z0-9_]+)", nm))
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and n in exported, n
-    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 17\b", hdr)
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mvdetr_ops_abi_version() == 17
+    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 18\b", hdr)
+    assert _lib.ABI_VERSION == 18 and _lib.lib().mvdetr_ops_abi_version() == 18
     import mvdetr_amd.ops as ops
     assert ops.ingest_frames is ingest_frames
 

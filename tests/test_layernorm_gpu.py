@@ -2,6 +2,8 @@
 import pytest
 import torch
 
+import layernorm_oracle as lo
+
 pytestmark = pytest.mark.gpu
 
 
@@ -27,6 +29,14 @@ def test_add_layer_norm_matches_torch(rows, cols, affine, with_res):
     assert got.shape == x.shape and got.dtype == torch.float32
     assert (got.double() - want64).abs().max().item() < 5e-6
     assert (got - want32).abs().max().item() < 5e-6
+    # the elementwise bar of tests/layernorm_oracle.py, and the instantiation that ran
+    from mvdetr_amd.ops.add_layernorm import last_kernel
+    assert last_kernel() == lo.FP32_KERNELS[cols]
+    w, b = (norm.weight.detach(), norm.bias.detach()) if affine else (None, None)
+    y, bar, _, _ = lo.oracle(x, res, w, b, norm.eps)
+    r = lo.ratio(got, y, bar)
+    print(f"LNBAR {last_kernel()} a/rows{2 * rows}_res{with_res:d}_affine{affine:d} out {r:.3f}")
+    assert r <= 1.0
 
 
 def test_add_layer_norm_training_and_other_shapes_use_torch(monkeypatch):
@@ -72,7 +82,7 @@ def test_encoder_layer_eval_uses_the_fused_tail_and_matches_training_mode_ops():
 
 @pytest.mark.parametrize("batch_pos", [False, True])
 def test_add_layer_norm_second_output(batch_pos):
-    from mvdetr_amd.ops.add_layernorm import add_layer_norm
+    from mvdetr_amd.ops.add_layernorm import add_layer_norm, last_kernel
     g = torch.Generator().manual_seed(3)
     x, res = torch.randn(2, 501, 128, generator=g).cuda(), torch.randn(2, 501, 128, generator=g).cuda()
     pos = torch.randn(2 if batch_pos else 1, 501, 128, generator=g).cuda()
@@ -82,6 +92,11 @@ def test_add_layer_norm_second_output(batch_pos):
         want = norm(x + res)
     assert (y - want).abs().max().item() < 5e-6
     assert (y2 - (want + pos)).abs().max().item() < 5e-6
+    assert last_kernel() == "add_layernorm_rows128x2"
+    w64, bar, w64_2, bar2 = lo.oracle(x, res, norm.weight.detach(), norm.bias.detach(), norm.eps, pos)
+    r, r2 = lo.ratio(y, w64, bar), lo.ratio(y2, w64_2, bar2)
+    print(f"LNBAR {last_kernel()} n01/second_output_B{pos.shape[0]} out {r:.3f} out2 {r2:.3f}")
+    assert r <= 1.0 and r2 <= 1.0
     # torch path (autograd needed) returns the same pair
     xg = x.clone().requires_grad_(True)
     z, z2 = add_layer_norm(xg, res, norm, then_add=pos)

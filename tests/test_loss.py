@@ -212,7 +212,7 @@ def test_header_declares_every_loss_export():
     assert want <= declared, want - declared
     from mvdetr_amd import _lib
     assert want <= set(_lib.SIGNATURES)
-    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 17\b", hdr) and _lib.ABI_VERSION == 17
+    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 18\b", hdr) and _lib.ABI_VERSION == 18
 
 
 def test_switch_and_route_predicates():

@@ -34,8 +34,8 @@ def test_new_symbols_are_declared_bound_and_exported_and_the_abi_version_stays()
         assert norm(proto) == norm(proto32), (name, proto)
         assert "const float *mean" in proto and "const float *var" in proto
         assert _lib.SIGNATURES[name] == _lib.SIGNATURES[re.sub(r"_b?f16$", "_f32", name)]
-    assert _lib.ABI_VERSION == 17 and lib.mvdetr_ops_abi_version() == 17
-    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 17\b", hdr)
+    assert _lib.ABI_VERSION == 18 and lib.mvdetr_ops_abi_version() == 18
+    assert re.search(r"#define MVDETR_OPS_ABI_VERSION 18\b", hdr)
 
 
 @pytest.mark.parametrize("suffix", ["f16", "bf16"])
