@@ -14,7 +14,10 @@
 //         register of accumulator p -- and nothing but the result is ever stored;
 //       * the input channels go by in chunks of 8: B^T d B is formed on the way into LDS (each lane transforms two channels
 //         of one tile from 16 8-byte loads), the U slice of the chunk is staged beside it; two LDS buffers, one barrier per
-//         chunk; the next chunk's loads are issued before the current chunk's MFMAs and written behind them;
+//         chunk.  With one wave per SIMD every instruction that is not an MFMA costs its issue slots in full (measured:
+//         docs/notes/conv_winograd.md), so the loop is built to need few of them -- buffer loads that return zero outside
+//         the image, LDS rows of 256 bytes reached by instruction offsets, scalar LDS-DMA addressing -- and deals them
+//         out one LDS read and one piece of the other work behind every MFMA;
 //       * dilation d: the convolution is d*d independent undilated ones on the sub-lattices (y mod d, x mod d); a tile is
 //         (image, sub-lattice, tile row, tile column) and its pixels are d apart -- no copies.  Every sub-lattice gets the
 //         tile grid of the largest one; pixels outside the image read as zero and are never stored.
@@ -34,12 +37,17 @@ namespace wino {
 constexpr int TILES = 64;                  // 2x2 output tiles per workgroup
 constexpr int KB = 64;                     // output channels per workgroup
 constexpr int CC = 8;                      // input channels per chunk
-constexpr int VROW = TILES + 4;            // floats per (position, channel) row of V: 68 keeps the four channel pairs that
-                                           // one half-wave writes together on different banks
-constexpr int V_FLOATS = 16 * CC * VROW;   // 8,704
+constexpr int VROW = TILES;                // floats per (position, channel) row of V: 256 bytes, so rows are reached by the
+                                           // st64 offsets of ds_read2 / ds_write2; the column of tile t in the rows of
+                                           // channel pair cp is t ^ 8 cp, which keeps the four channel pairs that one
+                                           // half-wave writes together on different banks
+constexpr int V_FLOATS = 16 * CC * VROW;   // 8,192
 constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
 constexpr int BUF_FLOATS = V_FLOATS + U_FLOATS;
-constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TILES * 8;      // two buffers + the tiles' output descriptors = 135,680
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TILES * 8;      // two buffers + the tiles' output descriptors = 131,584
+
+// Range of the x buffer resource and the offset of a pixel outside the image (beyond it: the load returns zero)
+constexpr unsigned X_RANGE = 0xFFFFFFF0u, X_OUTSIDE = 0xFFFFFFF8u;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
@@ -78,7 +86,8 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int *const tinfo = reinterpret_cast<int *>(lds + 2 * BUF_FLOATS);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               // uniform: LDS-DMA targets by scalar arithmetic
     // workgroups that share a 64-channel slice of U are 'kblocks' apart: with 8 (or 4, 2, 1) slices, consecutive ids being
     // dealt round-robin over the 8 XCDs, each XCD's L2 serves one slice
     const int kb = blockIdx.x % s.kblocks;
@@ -96,7 +105,6 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     const int ltile = tid >> 2, cp = tid & 3;
     int n, y0, x0;
     const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
-    unsigned mask = 0;                                                        // bit 4 i + j: input pixel (i, j) is in the image
     unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel pair cp
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -104,8 +112,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         for (int j = 0; j < 4; ++j) {
             const int yy = y0 + (i - 1) * d, xx = x0 + (j - 1) * d;
             const bool ok = tvalid && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            mask |= ok ? 1u << (4 * i + j) : 0u;
-            off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : 0u;
+            off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : X_OUTSIDE;
         }
     }
 
@@ -125,96 +132,153 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     const char *const ublk = reinterpret_cast<const char *>(U + kb * KB);
     const size_t ustep = (size_t)2 * C * K * 4;                               // two positions further per r, bytes
 
+    // The x loads are raw buffer loads: the uniform base (image block + chunk) travels in SGPRs, the lane's 32-bit byte
+    // offset in one VGPR, and a pixel outside the image has an offset past the buffer's range, for which the hardware
+    // returns zero -- no per-lane 64-bit addresses, no selects.  (Valid offsets end below 2^32 - 64: the host's bound.)
     float2 raw[16];
-    auto issue_loads = [&](int c0, float *ubuf) {
-        const char *const xc = reinterpret_cast<const char *>(xblk + c0);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) raw[e] = *reinterpret_cast<const float2 *>(xc + off[e]);
-        const char *const uc = ublk + (size_t)c0 * K * 4;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            __builtin_amdgcn_global_load_lds((global_void *)(uc + r * ustep + uoff), (lds_void *)(ubuf + r * 1024 + wave * 256),
-                                             16, 0, 0);
+    const __amdgpu_buffer_rsrc_t xrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(xblk), 0, (int)X_RANGE, 0x00020000);
+    auto load_x = [&](int c0, int e) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b64(xrsrc, (int)off[e], c0 * 4, 0);
+        static_assert(sizeof(v) == 8, "two floats");
+        raw[e] = __builtin_bit_cast(float2, v);
     };
-    // rows xi of B^T d B for both channels of the pair -> V[buf][4 xi + nu][2 cp + e][ltile]
-    auto transform_row = [&](float *vbuf, int xi) {
-        const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;                 // t = d[ra] -/+ d[rb]
-        float tx[4], ty[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float2 a = raw[4 * ra + j], b = raw[4 * rb + j];
-            const bool oka = mask >> (4 * ra + j) & 1, okb = mask >> (4 * rb + j) & 1;
-            const float ax = oka ? a.x : 0.f, ay = oka ? a.y : 0.f, bx = okb ? b.x : 0.f, by = okb ? b.y : 0.f;
-            if (xi == 0 || xi == 3) { tx[j] = ax - bx; ty[j] = ay - by; }     // d0 - d2, d1 - d3
-            else if (xi == 1) { tx[j] = ax + bx; ty[j] = ay + by; }           // d1 + d2
-            else { tx[j] = bx - ax; ty[j] = by - ay; }                        // d2 - d1
+    auto load_u = [&](int c0, float *ubuf, int r) {
+        const char *const uc = ublk + ((size_t)c0 * K * 4 + r * ustep);       // uniform: scalar arithmetic
+        unsigned o = uoff;
+        asm volatile("" : "+v"(o));                                           // keeps base + zext(offset) beside the load
+        __builtin_amdgcn_global_load_lds((global_void *)(uc + (uint64_t)o), (lds_void *)(ubuf + r * 1024 + wave * 256), 16, 0, 0);
+    };
+    // One sixteenth of a chunk's loads: the 16 x loads go first (two per piece), the 8 LDS-DMA of U behind them.
+    auto load_piece = [&](int c0, float *ubuf, int q) {
+        if (q < 8) {
+            load_x(c0, 2 * q);
+            load_x(c0, 2 * q + 1);
+        } else {
+            load_u(c0, ubuf, q - 8);
         }
-        float *const v0 = vbuf + (4 * xi * CC + 2 * cp) * VROW + ltile;
-        v0[0 * CC * VROW] = tx[0] - tx[2];
-        v0[1 * CC * VROW] = tx[1] + tx[2];
-        v0[2 * CC * VROW] = tx[2] - tx[1];
-        v0[3 * CC * VROW] = tx[1] - tx[3];
-        v0[0 * CC * VROW + VROW] = ty[0] - ty[2];
-        v0[1 * CC * VROW + VROW] = ty[1] + ty[2];
-        v0[2 * CC * VROW + VROW] = ty[2] - ty[1];
-        v0[3 * CC * VROW + VROW] = ty[1] - ty[3];
+    };
+
+    // B^T d B of the lane's tile and channel pair, in 24 pieces that fit between two MFMAs each:
+    //   pieces 6 xi + {0, 1}   the row combinations tx/ty of row xi
+    //   pieces 6 xi + {2..5}   the four values of row xi for both channels -> V[buf][4 xi + nu][2 cp + e][ltile ^ 8 cp]
+    float tx[4], ty[4];
+    const int v_off = 2 * cp * VROW + (ltile ^ (8 * cp));
+    auto xform_piece = [&](float *vbuf, int u) {
+        const int xi = u / 6, s = u % 6;
+        const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;                 // t = d[ra] -/+ d[rb]
+        if (s < 2) {
+#pragma unroll
+            for (int j = 2 * s; j < 2 * s + 2; ++j) {
+                const float2 a = raw[4 * ra + j], b = raw[4 * rb + j];
+                if (xi == 0 || xi == 3) { tx[j] = a.x - b.x; ty[j] = a.y - b.y; }     // d0 - d2, d1 - d3
+                else if (xi == 1) { tx[j] = a.x + b.x; ty[j] = a.y + b.y; }           // d1 + d2
+                else { tx[j] = b.x - a.x; ty[j] = b.y - a.y; }                        // d2 - d1
+            }
+            return;
+        }
+        const int nu = s - 2;
+        float *const v0 = vbuf + v_off + (4 * xi + nu) * CC * VROW;
+        if (nu == 0) { v0[0] = tx[0] - tx[2]; v0[VROW] = ty[0] - ty[2]; }
+        else if (nu == 1) { v0[0] = tx[1] + tx[2]; v0[VROW] = ty[1] + ty[2]; }
+        else if (nu == 2) { v0[0] = tx[2] - tx[1]; v0[VROW] = ty[2] - ty[1]; }
+        else { v0[0] = tx[1] - tx[3]; v0[VROW] = ty[1] - ty[3]; }
     };
 
     // ---- the wave's block of the sixteen products -----------------------------------------------------------------------------
     const int wm = wave & 1, wn = wave >> 1;                                  // 32-tile block, 32-channel block
-    const int a_off = (lane >> 5) * VROW + wm * 32 + (lane & 31);             // + (p * CC + 2 s) * VROW
+    int a_off[4];                                                             // k-step s: + (p * CC + 2 s) * VROW
+#pragma unroll
+    for (int st = 0; st < 4; ++st) a_off[st] = (lane >> 5) * VROW + ((wm * 32 + (lane & 31)) ^ (8 * st));
     const int b_off = V_FLOATS + (lane >> 5) * KB + wn * 32 + (lane & 31);    // + (p * CC + 2 s) * KB
     f32x16 acc[16];
+
+    // Two sets of operand registers, by the parity of the k-step: while the sixteen MFMAs of one k-step issue, the
+    // operands of the next one are read, one LDS instruction behind every MFMA -- positions p and p + 1 are eight rows
+    // (2,048 bytes) apart in V and in U, which is one ds_read2st64_b32 and no address arithmetic.
+    float fa[2][16], fb[2][16];
+    auto read_piece = [&](const float *buf, int st, int q) {
+        const int par = st & 1, p = 2 * (q & 7);
+        if (q < 8) {
+            fa[par][p] = buf[a_off[st] + (p * CC + 2 * st) * VROW];
+            fa[par][p + 1] = buf[a_off[st] + ((p + 1) * CC + 2 * st) * VROW];
+        } else {
+            fb[par][p] = buf[b_off + (p * CC + 2 * st) * KB];
+            fb[par][p + 1] = buf[b_off + ((p + 1) * CC + 2 * st) * KB];
+        }
+    };
+    auto mfma = [&](int p, int par) { acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[par][p], fb[par][p], acc[p], 0, 0, 0); };
+
+    const int chunks = C / CC;
+
+    // prologue: chunk 0 into buffer 0; then chunk 1's loads, and the operands of chunk 0's first k-step
+    {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) load_piece(0, lds + V_FLOATS, q);
+#pragma unroll
+        for (int u = 0; u < 24; ++u) xform_piece(lds, u);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this wave's LDS-DMA has landed
+        __syncthreads();
+        const int c1 = (1 < chunks ? 1 : 0) * CC;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            read_piece(lds, 0, q);
+            load_piece(c1, lds + BUF_FLOATS + V_FLOATS, q);
+        }
+    }
+
+    // One chunk = four groups of sixteen MFMAs (k-steps 0..3), one MFMA per position, and behind every MFMA one LDS read of
+    // the next k-step's operands plus one piece of the other work.  With one wave per SIMD nothing else hides the issue
+    // slots of that other work (profiles/conv_winograd_loop_ab.txt), so it is spread evenly and kept short:
+    //   k-step 0   nothing else: the next chunk's loads, issued a group earlier, get this group too (2,048 cycles)
+    //   k-step 1   the first half of the next chunk's B^T d B and its LDS writes
+    //   k-step 2   the second half
+    //   barrier    every wave's V writes and LDS-DMA of the next chunk are done, all reads of this chunk are done
+    //   k-step 3   its reads are the NEXT chunk's k-step 0; the loads of the chunk after it, into the buffer this chunk left
+    // No branch in the loop: past the last chunk the loads stage the last chunk again, into buffers nobody reads.
+    __builtin_amdgcn_sched_barrier(0);                                        // the 256 zeros are not live over the prologue
 #pragma unroll
     for (int p = 0; p < 16; ++p)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-
-    float fa[2][16], fb[2][16];                                               // the operands of two k-steps
-    auto read_step = [&](const float *buf, int st, int set) {
+    int ch = 0;                                                               // the host refuses C < 8: at least one chunk
+    do {
+        float *const cur = lds + (ch & 1) * BUF_FLOATS;
+        float *const nxt = lds + ((ch & 1) ^ 1) * BUF_FLOATS;
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
-            fa[set][p] = buf[a_off + (p * CC + 2 * st) * VROW];
-            fb[set][p] = buf[b_off + (p * CC + 2 * st) * KB];
+            mfma(p, 0);
+            read_piece(cur, 1, p);
+            __builtin_amdgcn_sched_barrier(0);
         }
-    };
-    auto mfma_step = [&](int set) {
 #pragma unroll
-        for (int p = 0; p < 16; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][p], fb[set][p], acc[p], 0, 0, 0);
-    };
-
-    // prologue: chunk 0 into buffer 0
-    issue_loads(0, lds + V_FLOATS);
+        for (int p = 0; p < 16; ++p) {
+            mfma(p, 1);
+            read_piece(cur, 2, p);
+            if (p >= 4) xform_piece(nxt, p - 4);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
-    for (int xi = 0; xi < 4; ++xi) transform_row(lds, xi);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // this wave's LDS-DMA has landed
-    __syncthreads();
-
-    const int chunks = C / CC;
-    for (int ch = 0; ch < chunks; ++ch) {
-        const float *const cur = lds + (ch & 1) * BUF_FLOATS;
-        float *const nxt = lds + ((ch & 1) ^ 1) * BUF_FLOATS;
-        // The next chunk goes into nxt, which was read last before the barrier that ended the previous iteration.  No
-        // branch in the loop: the last iteration stages the last chunk once more, into the buffer nobody reads again.
-        issue_loads((ch + 1 < chunks ? ch + 1 : ch) * CC, nxt + V_FLOATS);
-        read_step(cur, 0, 0);
-        read_step(cur, 1, 1);
-        mfma_step(0);
-        mfma_step(1);
-        // nothing of the transform moves above this line: its first instruction waits for the loads, which get the two
-        // steps above (2,048 cycles of MFMA) to land; and the last two steps' operands are read before V's writes, which
-        // the compiler cannot tell from them
-        __builtin_amdgcn_sched_barrier(0);
-        read_step(cur, 2, 0);
-        read_step(cur, 3, 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int xi = 0; xi < 4; ++xi) transform_row(nxt, xi);
-        mfma_step(0);
-        mfma_step(1);
+        for (int p = 0; p < 16; ++p) {
+            mfma(p, 0);
+            read_piece(cur, 3, p);
+            if (p < 12) xform_piece(nxt, 12 + p);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-    }
+        const int c2 = (ch + 2 < chunks ? ch + 2 : chunks - 1) * CC;
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+            mfma(p, 1);
+            read_piece(nxt, 0, p);
+            load_piece(c2, cur + V_FLOATS, p);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } while (++ch < chunks);
+    // the loads of the last k-step 3 are nobody's, but an LDS-DMA must not outlive the workgroup's LDS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     // ---- A^T M A in registers, then the stores ------------------------------------------------------------------------------------
     const int kcol = wn * 32 + (lane & 31);
@@ -240,7 +304,11 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
                 if (flags & 2) o[(size_t)d * W * K + (size_t)d * K] = y11;
             }
         }
-        __builtin_amdgcn_sched_barrier(0);                                    // one register's sixteen reads at a time
+        // one register's sixteen reads at a time, and the accumulators stay where the MFMAs left them: copied out all at
+        // once they take the whole VGPR file, and the allocator then spills the loop's operands to make room
+#pragma unroll
+        for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p]));
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -295,7 +363,8 @@ extern "C" int mvdetr_conv3x3_winograd_f32(const float *x, const float *U, float
         !aligned(U, 16) || !aligned(y, 16))
         return (int)hipErrorNotSupported;
     // a lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
-    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one)
+    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C is a multiple of 8, so the bound keeps every
+    // offset below 2^32 - 64, under the range of the kernel's x buffer (wino::X_RANGE)
     if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
     if (N == 0) return 0;
     wino::Shape s;
