@@ -380,8 +380,25 @@ int64_t mvdetr_trunk_launch_count(void);
 int mvdetr_winograd_weights_f32(const float *w, int C, int K, float *U, void *stream);
 int mvdetr_conv3x3_winograd_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K, int dilation,
                                 void *stream);
-/* Name of the kernel the last call of the two above launched ("none" before the first) and their launch count. */
+/* The same convolution with the block's inference epilogue applied in the output store (additive entry):
+ *     y = act( conv(x)*s + t  [+ res]  [+ res*s2 + t2] )
+ * with s, t, s2, t2, act and the BatchNorm / residual arguments exactly as in mvdetr_bn_act_f32, in its argument order and
+ * its arithmetic, element for element: the result has the bits of mvdetr_conv3x3_winograd_f32 followed by mvdetr_bn_act_f32
+ * in place, without the pass over y.  The BatchNorm vectors are [K] (4-byte aligned here: a lane reads one channel);
+ * res [N, H, W, K] is y's geometry, 16-byte aligned, only read, and only where y is stored.
+ * Refusals: those of mvdetr_conv3x3_winograd_f32; hipErrorInvalidValue for a missing mean / var, for a residual BatchNorm
+ * without a residual, and for a residual whose byte range overlaps y's. */
+int mvdetr_conv3x3_winograd_bn_act_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K,
+                                       int dilation, const float *mean, const float *var, const float *gamma,
+                                       const float *beta, float eps, const float *res, const float *res_mean,
+                                       const float *res_var, const float *res_gamma, const float *res_beta, float res_eps,
+                                       int relu, void *stream);
+/* Name of the kernel the last call of the three above launched ("none" before the first) and their launch count: one per
+ * call; the convolution's name is "conv3x3_winograd_f32" whatever its store applies. */
 const char *mvdetr_winograd_last_kernel(void);
+/* What the last convolution's store applied: "none", "bn", "bn_add" or "bn_bn_add", with "_relu" appended under ReLU
+ * (mvdetr_trunk_last_kernel's names). */
+const char *mvdetr_winograd_last_epilogue(void);
 int64_t mvdetr_winograd_launch_count(void);
 
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------

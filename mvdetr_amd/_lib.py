@@ -100,7 +100,10 @@ SIGNATURES = {
     "mvdetr_trunk_launch_count": ([], ctypes.c_int64),
     "mvdetr_winograd_weights_f32": ([_vp, _i, _i, _vp, _vp], _i),
     "mvdetr_conv3x3_winograd_f32": ([_vp] * 3 + [_i] * 6 + [_vp], _i),
+    "mvdetr_conv3x3_winograd_bn_act_f32": ([_vp] * 3 + [_i] * 6 + [_vp] * 4 + [ctypes.c_float] + [_vp] * 5
+                                           + [ctypes.c_float, _i, _vp], _i),
     "mvdetr_winograd_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_winograd_last_epilogue": ([], ctypes.c_char_p),
     "mvdetr_winograd_launch_count": ([], ctypes.c_int64),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f64": (_WARP, _i),

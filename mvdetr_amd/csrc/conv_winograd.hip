@@ -22,6 +22,7 @@
 //         (image, sub-lattice, tile row, tile column) and its pixels are d apart -- no copies.  Every sub-lattice gets the
 //         tile grid of the largest one; pixels outside the image read as zero and are never stored.
 //   No atomics, no split over the input channels: the result is deterministic.
+#include "bn_epilogue.h"
 #include "common.h"
 #include "../../include/mvdetr_ops.h"
 
@@ -30,6 +31,7 @@
 namespace mvdetr {
 
 static std::atomic<const char *> g_winograd_last_kernel{"none"};
+static std::atomic<const char *> g_winograd_last_epilogue{"none"};
 static std::atomic<int64_t> g_winograd_launches{0};
 
 namespace wino {
@@ -78,8 +80,17 @@ __device__ __forceinline__ bool tile_origin(const Shape &s, unsigned t, int &n, 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void global_void;
 
+// What the output store applies (MODE 0: nothing, and none of this is read).  res has y's [N, H, W, K] geometry.
+struct Epilogue {
+    BnVectors bn, bn2;
+    const float *res;
+};
+
+// MODE 0: y = conv(x).  1: y = act(bn(conv)).  2: act(bn(conv) + res).  3: act(bn(conv) + bn2(res)).  The arithmetic after
+// the convolution is bn_act_cl's (bn_epilogue.h), element for element: the same bits as the pass over a stored y.
+template <int MODE, bool RELU>
 __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restrict__ x, const float *__restrict__ U,
-                                                            float *__restrict__ y, const Shape s)
+                                                            float *__restrict__ y, const Shape s, const Epilogue ep)
 {
     // ONE shared array: two {V, U} buffers, then the tiles' output descriptors {pixel offset from the workgroup's first
     // image, flags}
@@ -282,6 +293,38 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
 
     // ---- A^T M A in registers, then the stores ------------------------------------------------------------------------------------
     const int kcol = wn * 32 + (lane & 31);
+    // The lane stores ONE output channel, kb * 64 + kcol: its BatchNorm constants, folded here on every call.
+    float bs = 1.f, bt = 0.f, bs2 = 0.f;
+    if (MODE >= 1) bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
+    if (MODE == 3) {
+        float bt2;
+        bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
+        bt = bt + bt2;
+    }
+    // The residual: every value this lane will add, 4 per accumulator register, requested before the first one is used --
+    // the loop's operand registers are dead, and with one workgroup per CU nothing else would hide a latency per register.
+    // Raw buffer loads as for x: the byte offsets of the stores below, and an element that is not stored gets an offset
+    // past the buffer's range, for which nothing is read.  The range ends with the tensor.
+    float q[16][4];
+    if (MODE >= 2) {
+        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, (int)(left < X_RANGE ? (unsigned)left : X_RANGE),
+            0x00020000);
+        const unsigned dx = (unsigned)d * K * 4u, dy = (unsigned)d * W * K * 4u;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int flags = tinfo[2 * t + 1];
+            const unsigned o = ((unsigned)tinfo[2 * t + 0] + kcol) * 4u;
+            const unsigned o4[4] = {(flags & 1) ? o : X_OUTSIDE, (flags & 3) == 3 ? o + dx : X_OUTSIDE,
+                                    (flags & 5) == 5 ? o + dy : X_OUTSIDE, (flags & 7) == 7 ? o + dy + dx : X_OUTSIDE};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                q[r][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
+        }
+        __builtin_amdgcn_sched_barrier(0);                                    // all of them are issued ahead of the first store
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);     // the accumulator's row = the tile
@@ -293,8 +336,15 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
             s0[nu] = acc[nu][r] + acc[4 + nu][r] + acc[8 + nu][r];
             s1[nu] = acc[4 + nu][r] - acc[8 + nu][r] - acc[12 + nu][r];
         }
-        const float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
-        const float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+        float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+        float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+        if (MODE >= 1) {
+            constexpr int RES = MODE - 1;
+            y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? q[r][0] : 0.f, bs2);
+            y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? q[r][1] : 0.f, bs2);
+            y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? q[r][2] : 0.f, bs2);
+            y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? q[r][3] : 0.f, bs2);
+        }
         float *const o = yblk + pix + kcol;
         if (flags & 1) {
             o[0] = y00;
@@ -336,7 +386,72 @@ __global__ __launch_bounds__(256) void winograd_weights_f32(const float *__restr
     }
 }
 
-static PerDevice<int> g_lds_attr;
+// One launch of one instantiation (its dynamic-LDS attribute is set once per device)
+template <int MODE, bool RELU>
+static int launch(hipStream_t st, unsigned blocks, const float *x, const float *U, float *y, const Shape &s, const Epilogue &ep)
+{
+    static PerDevice<int> lds_attr;
+    const int rc = lds_attr.get([] {
+        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_winograd_f32<MODE, RELU>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    });
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL((conv3x3_winograd_f32<MODE, RELU>), dim3(blocks), dim3(256), LDS_BYTES, st, x, U, y, s, ep);
+    return 0;
+}
+
+// [mode][relu], trunk_epilogue's names
+static const char *const kEpilogueNames[4][2] = {
+    {"none", "none"}, {"bn", "bn_relu"}, {"bn_add", "bn_add_relu"}, {"bn_bn_add", "bn_bn_add_relu"}};
+
+static bool bn_ok(const BnVectors &b)
+{
+    return b.mean && b.var && aligned(b.mean, 4) && aligned(b.var, 4) && aligned(b.gamma, 4) && aligned(b.beta, 4);
+}
+
+// mode 0: the convolution alone (ep unread).  1..3: with the epilogue in the store.
+static int conv_entry(const float *x, const float *U, float *y, int N, int H, int W, int C, int K, int dilation, int mode,
+                      bool relu, const Epilogue &ep, void *stream)
+{
+    if (!x || !U || !y || x == y || N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    if (mode >= 1 && !bn_ok(ep.bn)) return (int)hipErrorInvalidValue;
+    if (mode == 3 && !bn_ok(ep.bn2)) return (int)hipErrorInvalidValue;
+    if (C % 8 != 0 || K % 64 != 0 || !(dilation == 1 || dilation == 2 || dilation == 4) || !aligned(x, 16) ||
+        !aligned(U, 16) || !aligned(y, 16) || (mode >= 2 && !aligned(ep.res, 16)))
+        return (int)hipErrorNotSupported;
+    // a lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
+    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C is a multiple of 8, so the bound keeps every
+    // offset below 2^32 - 64, under the range of the kernel's x buffer (wino::X_RANGE)
+    if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
+    if (mode >= 2) {
+        // the residual is read while other workgroups store y: their byte ranges may not meet
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep.res), y0 = reinterpret_cast<uintptr_t>(y);
+        const uintptr_t bytes = (uintptr_t)N * H * W * K * 4;
+        if (r0 < y0 + bytes && y0 < r0 + bytes) return (int)hipErrorInvalidValue;
+    }
+    if (N == 0) return 0;
+    Shape s;
+    s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
+    s.th = ((H + dilation - 1) / dilation + 1) / 2;
+    s.tw = ((W + dilation - 1) / dilation + 1) / 2;
+    const int64_t tiles = (int64_t)N * dilation * dilation * s.th * s.tw;
+    s.kblocks = K / KB;
+    const int64_t blocks = (tiles + TILES - 1) / TILES * s.kblocks;
+    if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
+    s.tiles = (unsigned)tiles;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned nb = (unsigned)blocks;
+    int rc;
+    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep);
+    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep) : launch<1, false>(st, nb, x, U, y, s, ep);
+    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep) : launch<2, false>(st, nb, x, U, y, s, ep);
+    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep) : launch<3, false>(st, nb, x, U, y, s, ep);
+    if (rc != 0) return rc;
+    g_winograd_last_kernel = "conv3x3_winograd_f32";
+    g_winograd_last_epilogue = kEpilogueNames[mode][mode && relu ? 1 : 0];
+    g_winograd_launches.fetch_add(1);
+    return (int)hipGetLastError();
+}
 
 }  // namespace wino
 }  // namespace mvdetr
@@ -357,37 +472,24 @@ extern "C" int mvdetr_winograd_weights_f32(const float *w, int C, int K, float *
 extern "C" int mvdetr_conv3x3_winograd_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K,
                                            int dilation, void *stream)
 {
+    return mvdetr::wino::conv_entry(x, U, y, N, H, W, C, K, dilation, 0, false, mvdetr::wino::Epilogue{}, stream);
+}
+
+extern "C" int mvdetr_conv3x3_winograd_bn_act_f32(const float *x, const float *U, float *y, int N, int H, int W, int C, int K,
+                                                  int dilation, const float *mean, const float *var, const float *gamma,
+                                                  const float *beta, float eps, const float *res, const float *res_mean,
+                                                  const float *res_var, const float *res_gamma, const float *res_beta,
+                                                  float res_eps, int relu, void *stream)
+{
     using namespace mvdetr;
-    if (!x || !U || !y || x == y || N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return (int)hipErrorInvalidValue;
-    if (C % 8 != 0 || K % 64 != 0 || !(dilation == 1 || dilation == 2 || dilation == 4) || !aligned(x, 16) ||
-        !aligned(U, 16) || !aligned(y, 16))
-        return (int)hipErrorNotSupported;
-    // a lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
-    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C is a multiple of 8, so the bound keeps every
-    // offset below 2^32 - 64, under the range of the kernel's x buffer (wino::X_RANGE)
-    if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
-    if (N == 0) return 0;
-    wino::Shape s;
-    s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
-    s.th = ((H + dilation - 1) / dilation + 1) / 2;
-    s.tw = ((W + dilation - 1) / dilation + 1) / 2;
-    const int64_t tiles = (int64_t)N * dilation * dilation * s.th * s.tw;
-    s.kblocks = K / wino::KB;
-    const int64_t blocks = (tiles + wino::TILES - 1) / wino::TILES * s.kblocks;
-    if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
-    s.tiles = (unsigned)tiles;
-    const int rc = wino::g_lds_attr.get([] {
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(wino::conv3x3_winograd_f32),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, wino::LDS_BYTES);
-    });
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(wino::conv3x3_winograd_f32, dim3((unsigned)blocks), dim3(256), wino::LDS_BYTES,
-                       reinterpret_cast<hipStream_t>(stream), x, U, y, s);
-    g_winograd_last_kernel = "conv3x3_winograd_f32";
-    g_winograd_launches.fetch_add(1);
-    return (int)hipGetLastError();
+    const bool res_bn = res_mean || res_var || res_gamma || res_beta;
+    if (res_bn && !res) return (int)hipErrorInvalidValue;
+    const wino::Epilogue ep{BnVectors{mean, var, gamma, beta, eps}, BnVectors{res_mean, res_var, res_gamma, res_beta, res_eps}, res};
+    return wino::conv_entry(x, U, y, N, H, W, C, K, dilation, !res ? 1 : res_bn ? 3 : 2, relu != 0, ep, stream);
 }
 
 extern "C" const char *mvdetr_winograd_last_kernel(void) { return mvdetr::g_winograd_last_kernel.load(); }
+
+extern "C" const char *mvdetr_winograd_last_epilogue(void) { return mvdetr::g_winograd_last_epilogue.load(); }
 
 extern "C" int64_t mvdetr_winograd_launch_count(void) { return mvdetr::g_winograd_launches.load(); }

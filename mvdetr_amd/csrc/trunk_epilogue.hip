@@ -15,6 +15,7 @@
 // Both families also exist over float16 / bfloat16 storage (eight channels per lane, fp32 arithmetic, one rounding): below.
 #include <atomic>
 
+#include "bn_epilogue.h"
 #include "common.h"
 #include "half_types.h"
 #include "../../include/mvdetr_ops.h"
@@ -24,28 +25,13 @@ namespace mvdetr {
 static std::atomic<const char *> g_trunk_last_kernel{"none"};
 static std::atomic<int64_t> g_trunk_launches{0};
 
-struct BnVectors {
-    const float *mean, *var, *gamma, *beta;                   // [C]; gamma / beta may be null (1 / 0)
-    float eps;
-};
-
-// scale and shift of four consecutive channels
-__device__ __forceinline__ void bn_fold4(const BnVectors &bn, int c, float4 &s, float4 &t)
-{
-    const float4 m = *reinterpret_cast<const float4 *>(bn.mean + c);
-    const float4 v = *reinterpret_cast<const float4 *>(bn.var + c);
-    const float4 g = bn.gamma ? *reinterpret_cast<const float4 *>(bn.gamma + c) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float4 b = bn.beta ? *reinterpret_cast<const float4 *>(bn.beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    s = make_float4(g.x / sqrtf(v.x + bn.eps), g.y / sqrtf(v.y + bn.eps), g.z / sqrtf(v.z + bn.eps), g.w / sqrtf(v.w + bn.eps));
-    t = make_float4(b.x - m.x * s.x, b.y - m.y * s.y, b.z - m.z * s.z, b.w - m.w * s.w);
-}
-
-__device__ __forceinline__ float relu_nan(float z) { return z < 0.f ? 0.f : z; }              // NaN stays NaN
+// BnVectors, bn_fold4 (s and t of four consecutive channels), relu_nan and the finishing step: bn_epilogue.h, shared with
+// the Winograd convolution's fused store
 __device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }   // torch's pooling update
 
 __device__ __forceinline__ float4 fma4(float4 x, float4 s, float4 t)
 {
-    return make_float4(x.x * s.x + t.x, x.y * s.y + t.y, x.z * s.z + t.z, x.w * s.w + t.w);
+    return make_float4(bn_apply(x.x, s.x, t.x), bn_apply(x.y, s.y, t.y), bn_apply(x.z, s.z, t.z), bn_apply(x.w, s.w, t.w));
 }
 
 // MODE 0: no residual; 1: + r; 2: + (r*s2 + t2).  x, r, y: [rows, C] (channel-last).  The block is TX lanes wide over the
@@ -66,10 +52,8 @@ __global__ __launch_bounds__(256) void bn_act_cl(const float *x, BnVectors bn, c
         t = make_float4(t.x + t2.x, t.y + t2.y, t.z + t2.z, t.w + t2.w);
     }
     auto finish = [&](float4 z, float4 q) {
-        if (MODE == 1) z = make_float4(z.x + q.x, z.y + q.y, z.z + q.z, z.w + q.w);
-        if (MODE == 2) z = fma4(q, s2, z);
-        if (RELU) z = make_float4(relu_nan(z.x), relu_nan(z.y), relu_nan(z.z), relu_nan(z.w));
-        return z;
+        return make_float4(bn_finish<MODE, RELU>(z.x, q.x, s2.x), bn_finish<MODE, RELU>(z.y, q.y, s2.y),
+                           bn_finish<MODE, RELU>(z.z, q.z, s2.z), bn_finish<MODE, RELU>(z.w, q.w, s2.w));
     };
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (; row + step < rows; row += 2 * step) {

@@ -19,7 +19,8 @@ from torch import nn
 
 from . import geometry
 from .ops import warp_perspective
-from .ops.conv_winograd import winograd_conv3x3, winograd_conv3x3_available
+from .ops.conv_winograd import (winograd_conv3x3, winograd_conv3x3_available, winograd_conv3x3_bn_act,
+                                winograd_conv3x3_bn_act_available)
 from .ops.detect import bev_detect
 from .ops.ingest import ingest_frames
 from .ops.trunk_epilogue import (bn_act, bn_act_half, bn_relu_maxpool, bn_relu_maxpool_half, fused_bn_act_available,
@@ -76,6 +77,35 @@ def _bn_add_relu(out, bn, x, downsample, relu):
     return relu(bn(out) + identity)
 
 
+def _conv3x3_bn_relu(x, conv, bn, relu):
+    """relu(bn(conv(x))): one Winograd launch with the epilogue in its store where that takes these arguments, the
+    convolution and the pass behind it otherwise."""
+    if type(relu) is nn.ReLU and winograd_conv3x3_bn_act_available(x, conv, bn):
+        return winograd_conv3x3_bn_act(x, conv, bn, relu=True)
+    return _bn_relu(_conv3x3(x, conv), bn, relu)
+
+
+def _conv3x3_bn_add_relu(out, conv, bn, x, downsample, relu):
+    """The tail of a BasicBlock, relu(bn(conv(out)) + identity), as one Winograd launch that reads the identity branch in
+    its store -- x itself, or the downsample convolution's raw output (run first) through its BatchNorm; x is never
+    written -- where that takes these arguments, and as _conv3x3 + _bn_add_relu otherwise."""
+    if type(relu) is nn.ReLU:
+        if downsample is None:
+            if winograd_conv3x3_bn_act_available(out, conv, bn, x):
+                return winograd_conv3x3_bn_act(out, conv, bn, x, relu=True)
+        elif type(downsample) is nn.Sequential and len(downsample) == 2 and type(downsample[0]) is nn.Conv2d \
+                and winograd_conv3x3_bn_act_available(out, conv, bn):
+            raw = downsample[0](x)
+            if winograd_conv3x3_bn_act_available(out, conv, bn, raw, downsample[1]):
+                return winograd_conv3x3_bn_act(out, conv, bn, raw, downsample[1], relu=True)
+            y = _conv3x3(out, conv)
+            op = _fused_bn_act(y, bn, raw, downsample[1])
+            if op is not None:
+                return op(y, bn, raw, downsample[1], relu=True, inplace=True)
+            return relu(bn(y) + downsample[1](raw))
+    return _bn_add_relu(_conv3x3(out, conv), bn, x, downsample, relu)
+
+
 class ResNetTrunk(nn.Sequential):
     """The trunk as the reference slices it -- conv1, bn1, relu, maxpool, layer1..4 at child indices 0..7, so parameter
     names are ``base.<index>...`` -- whose forward runs children 1-3 (BatchNorm, ReLU, MaxPool2d(3, 2, 1)) as one HIP
@@ -111,8 +141,8 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        out = _bn_relu(_conv3x3(x, self.conv1), self.bn1, self.relu)
-        return _bn_add_relu(_conv3x3(out, self.conv2), self.bn2, x, self.downsample, self.relu)
+        out = _conv3x3_bn_relu(x, self.conv1, self.bn1, self.relu)
+        return _conv3x3_bn_add_relu(out, self.conv2, self.bn2, x, self.downsample, self.relu)
 
 
 class Bottleneck(nn.Module):
@@ -134,7 +164,7 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         out = _bn_relu(self.conv1(x), self.bn1, self.relu)
-        out = _bn_relu(_conv3x3(out, self.conv2), self.bn2, self.relu)
+        out = _conv3x3_bn_relu(out, self.conv2, self.bn2, self.relu)
         return _bn_add_relu(self.conv3(out), self.bn3, x, self.downsample, self.relu)
 
 

@@ -4,6 +4,10 @@ activations, stride 1, padding = dilation in {1, 2, 4}, no bias, and only the (C
 faster than MIOpen's pick; everything else keeps torch's convolution: the callers in model.py ask the
 predicate first.
 
+The block's inference epilogue -- BatchNorm, the residual (as it is or through the downsample BatchNorm) and ReLU -- can be
+applied in the kernel's output store (winograd_conv3x3_bn_act): bn_act's arithmetic on the value a lane is about to store,
+so the bits of winograd_conv3x3 followed by bn_act in place, without that pass over the output.
+
 The transformed weights U = G g G^T (fp64, rounded once) are built once per weight tensor and cached."""
 from __future__ import annotations
 
@@ -14,8 +18,10 @@ import torch
 from torch import nn
 
 from .. import _lib
+from . import trunk_epilogue
 
 _enabled = os.environ.get("MVDETR_TRUNK_WINOGRAD", "1") != "0"
+_epilogue = os.environ.get("MVDETR_WINOGRAD_EPILOGUE", "1") != "0"
 
 # F(2x2, 3x3):  Y = A^T [ (G g G^T) .* (B^T d B) ] A.  The kernels hard-code these (winograd_weights_f32 forms G g G^T,
 # the convolution's loader B^T d B and its epilogue A^T M A); tests/test_conv_winograd.py pins them against a direct form.
@@ -46,6 +52,19 @@ def trunk_winograd_enabled() -> bool:
     return _enabled
 
 
+def set_winograd_epilogue(on: bool) -> bool:
+    """Switch the epilogue in the convolution's store on or off for this process (default on; ``MVDETR_WINOGRAD_EPILOGUE=0``
+    starts with it off).  Returns the previous setting.  Off: the convolution stores its plain output and the epilogue is
+    the pass of its own (ops/trunk_epilogue.py), bit for bit the same result."""
+    global _epilogue
+    prev, _epilogue = _epilogue, bool(on)
+    return prev
+
+
+def winograd_epilogue_enabled() -> bool:
+    return _epilogue
+
+
 def set_winograd_min_pixels(pixels: int) -> int:
     """The pixel floor of winograd_conv3x3_available() (MIN_PIXELS by default); returns the previous one.  For tests, which
     run the model on small images."""
@@ -57,6 +76,12 @@ def set_winograd_min_pixels(pixels: int) -> int:
 def last_kernel() -> str:
     """Name of the kernel the last Winograd call of this process launched ("none" before the first)."""
     return _lib.lib().mvdetr_winograd_last_kernel().decode()
+
+
+def last_epilogue() -> str:
+    """What the last Winograd convolution's store applied: "none", "bn", "bn_add" or "bn_bn_add", with "_relu" appended
+    under ReLU (trunk_epilogue.last_kernel's names)."""
+    return _lib.lib().mvdetr_winograd_last_epilogue().decode()
 
 
 def launch_count() -> int:
@@ -156,4 +181,45 @@ def winograd_conv3x3(x: torch.Tensor, conv: nn.Conv2d, force: bool = False) -> t
         code = _lib.lib().mvdetr_conv3x3_winograd_f32(x.data_ptr(), U.data_ptr(), y.data_ptr(), N, H, W, C, K,
                                                       conv.dilation[0], _lib.current_stream_ptr(x.device))
     _lib.check(code, "conv3x3_winograd")
+    return y
+
+
+def _epilogue_ok(x, conv, bn, residual, residual_bn) -> bool:
+    """The epilogue's own conditions, for the output [N, K, H, W] that ``conv(x)`` would have."""
+    shape = (x.shape[0], conv.out_channels, x.shape[2], x.shape[3])
+    return trunk_epilogue.bn_act_conditions(shape, x.dtype, x.device, x.requires_grad, bn, residual, residual_bn)
+
+
+def winograd_conv3x3_bn_act_available(x: torch.Tensor, conv: nn.Module, bn: nn.Module, residual: torch.Tensor = None,
+                                      residual_bn: nn.Module = None) -> bool:
+    """True when the model runs ``act(bn(conv(x)) [+ residual | + residual_bn(residual)])`` as ONE Winograd launch:
+    winograd_conv3x3_available(x, conv), the trunk's fused epilogues switched on (``set_trunk_fusion``), this module's
+    own switch on (``set_winograd_epilogue``), and the BatchNorm / residual conditions of fused_bn_act_available() for
+    the convolution's output.  fp32 only: 16-bit activations never take the kernel."""
+    return (_epilogue and trunk_epilogue.trunk_fusion_enabled() and winograd_conv3x3_available(x, conv)
+            and _epilogue_ok(x, conv, bn, residual, residual_bn))
+
+
+def winograd_conv3x3_bn_act(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, residual: torch.Tensor = None,
+                            residual_bn: nn.BatchNorm2d = None, relu: bool = True, force: bool = False) -> torch.Tensor:
+    """``act(bn(conv(x)) [+ residual | + residual_bn(residual)])`` in one launch: a fresh channel-last tensor with the bits
+    of ``bn_act(winograd_conv3x3(x, conv), bn, residual, residual_bn, relu=relu, inplace=True)``.  The residual is only
+    read.  ``force`` skips the switches, the family table, the pixel floor and the cudnn.deterministic rule, as in
+    winograd_conv3x3.  Raises when the arguments do not take the kernel."""
+    ok = (_structure_ok(x, conv) and _epilogue_ok(x, conv, bn, residual, residual_bn)) if force \
+        else winograd_conv3x3_bn_act_available(x, conv, bn, residual, residual_bn)
+    if not ok:
+        raise RuntimeError("winograd_conv3x3_bn_act: these arguments do not take the kernel "
+                           "(see winograd_conv3x3_bn_act_available)")
+    U = _transformed_weights(conv.weight)
+    N, C, H, W = x.shape
+    K = conv.out_channels
+    y = torch.empty((N, K, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    bn_args = trunk_epilogue._bn_args
+    with torch.cuda.device(x.device):
+        code = _lib.lib().mvdetr_conv3x3_winograd_bn_act_f32(
+            x.data_ptr(), U.data_ptr(), y.data_ptr(), N, H, W, C, K, conv.dilation[0], *bn_args(bn),
+            0 if residual is None else residual.data_ptr(), *bn_args(residual_bn), int(bool(relu)),
+            _lib.current_stream_ptr(x.device))
+    _lib.check(code, "conv3x3_winograd_bn_act")
     return y

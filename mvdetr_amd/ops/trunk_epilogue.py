@@ -42,9 +42,13 @@ def launch_count() -> int:
 HALF_DTYPES = (torch.float16, torch.bfloat16)
 
 
+def _on_device(t) -> bool:
+    return t.is_cuda
+
+
 def _activation_ok(x, dtypes=(torch.float32,), vec=4) -> bool:
     # channel-last memory, dense: the kernels index it as [N*H*W, C]; a lane owns `vec` channels (16 bytes)
-    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in dtypes and x.dim() == 4 and x.shape[1] % vec == 0
+    return (isinstance(x, torch.Tensor) and _on_device(x) and x.dtype in dtypes and x.dim() == 4 and x.shape[1] % vec == 0
             and x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0)
 
 
@@ -54,32 +58,43 @@ def _overlap(a, b) -> bool:
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def _vector_ok(v, x) -> bool:
-    return v.dtype == torch.float32 and v.device == x.device and v.is_contiguous() and v.data_ptr() % 16 == 0
+def _vector_ok(v, device) -> bool:
+    return v.dtype == torch.float32 and v.device == device and v.is_contiguous() and v.data_ptr() % 16 == 0
 
 
-def _bn_ok(bn, x) -> bool:
+def _bn_ok(bn, channels, device, requires_grad) -> bool:
     if not (type(bn) is nn.BatchNorm2d and not bn.training and bn.running_mean is not None and bn.running_var is not None
-            and bn.num_features == x.shape[1]):
+            and bn.num_features == channels):
         return False
     vecs = [bn.running_mean, bn.running_var] + [p for p in (bn.weight, bn.bias) if p is not None]
-    if not all(_vector_ok(v, x) for v in vecs):
+    if not all(_vector_ok(v, device) for v in vecs):
         return False
     # nothing that needs autograd: the kernels are forward only
-    return not (torch.is_grad_enabled() and (x.requires_grad or any(v.requires_grad for v in vecs)))
+    return not (torch.is_grad_enabled() and (requires_grad or any(v.requires_grad for v in vecs)))
 
 
-def _bn_act_ok(x, bn, residual, residual_bn, dtypes, vec) -> bool:
-    if not (_enabled and _activation_ok(x, dtypes, vec) and _bn_ok(bn, x)):
+def bn_act_conditions(shape, dtype, device, requires_grad, bn, residual=None, residual_bn=None, vec=4) -> bool:
+    """The BatchNorm and residual side of fused_bn_act_available() for an activation of this shape, dtype and device
+    that need not exist yet (a convolution asks before it allocates its output): BatchNorm2d modules in eval mode with
+    running statistics and fp32 vectors, a residual of the same shape, dtype and channel-last layout, nothing that needs
+    autograd.  The switch, the activation's own layout and its overlap with the residual are the caller's to check."""
+    if not _bn_ok(bn, shape[1], device, requires_grad):
         return False
     if residual is None:
         return residual_bn is None
-    if not (_activation_ok(residual, (x.dtype,), vec) and residual.shape == x.shape and residual.device == x.device
-            and not _overlap(residual, x)):
+    if not (_activation_ok(residual, (dtype,), vec) and residual.shape == torch.Size(shape) and residual.device == device):
         return False
     if torch.is_grad_enabled() and residual.requires_grad:
         return False
-    return residual_bn is None or _bn_ok(residual_bn, residual)
+    return residual_bn is None or _bn_ok(residual_bn, residual.shape[1], residual.device, residual.requires_grad)
+
+
+def _bn_act_ok(x, bn, residual, residual_bn, dtypes, vec) -> bool:
+    if not (_enabled and _activation_ok(x, dtypes, vec)):
+        return False
+    if not bn_act_conditions(x.shape, x.dtype, x.device, x.requires_grad, bn, residual, residual_bn, vec):
+        return False
+    return residual is None or not _overlap(residual, x)
 
 
 def fused_bn_act_available(x: torch.Tensor, bn: nn.Module, residual: torch.Tensor = None, residual_bn: nn.Module = None) -> bool:
@@ -142,7 +157,8 @@ def bn_act_half(x: torch.Tensor, bn: nn.BatchNorm2d, residual: torch.Tensor = No
 def _pool_ok(x, bn, relu, pool, dtypes, vec) -> bool:
     def two(v, want):
         return v == want or v == (want, want)
-    if not (_enabled and _activation_ok(x, dtypes, vec) and _bn_ok(bn, x) and type(relu) is nn.ReLU and type(pool) is nn.MaxPool2d):
+    if not (_enabled and _activation_ok(x, dtypes, vec) and _bn_ok(bn, x.shape[1], x.device, x.requires_grad)
+            and type(relu) is nn.ReLU and type(pool) is nn.MaxPool2d):
         return False
     cg = x.shape[1] // vec
     if not (256 % cg == 0 if cg <= 256 else cg % 256 == 0):

@@ -3,10 +3,16 @@ convolution (cudnn.benchmark = True, as bench.py sets: MIOpen picks by measureme
 MFMA kernel, interleaved in one process, HIP events.
 
     python tools/conv_bench.py [--reps 5] [--launches 20] [--out profiles/trunk_winograd_shapes.txt]
+    python tools/conv_bench.py --epilogue [--out profiles/conv_winograd_epilogue_shapes.txt]
 
 A repetition times `launches` back-to-back launches of one side, then of the other; a family is switched on in
 mvdetr_amd/ops/conv_winograd.py only where the kernel is faster in EVERY repetition.  Also prints each shape's deviation
-from an fp64 convolution for both sides (max-abs, on a post-ReLU N(0,1) input and kaiming weights)."""
+from an fp64 convolution for both sides (max-abs, on a post-ReLU N(0,1) input and kaiming weights).
+
+--epilogue times the convolution WITH the block's epilogue, for every epilogue the trunk runs behind each shape, three sides
+interleaved: (a) torch's convolution + bn_act in place, (b) the plain Winograd kernel + bn_act in place, (c) the Winograd
+kernel with the epilogue in its store.  Besides the six layer3/4 shapes it times the two layer1/2 candidates at their own
+sizes; the same rule decides about them: (c) faster than (a) in every repetition, for every epilogue."""
 import argparse
 import os
 import sys
@@ -21,6 +27,15 @@ SHAPES = [  # name, C, K, dilation
     ("layer4.0.conv1", 256, 512, 2), ("layer4.x.conv2", 512, 512, 1), ("layer4.1.conv1", 512, 512, 4),
 ]
 
+# --epilogue: name, C, K, dilation, the epilogues the trunk runs behind it, pixels (None: --pixels)
+EPILOGUE_SHAPES = [
+    ("layer3.0.conv1", 128, 256, 1, ("bn",), None), ("layer3.x.conv2", 256, 256, 1, ("bn_add", "bn_bn_add"), None),
+    ("layer3.1.conv1", 256, 256, 2, ("bn",), None), ("layer4.0.conv1", 256, 512, 2, ("bn",), None),
+    ("layer4.x.conv2", 512, 512, 1, ("bn_add", "bn_bn_add"), None), ("layer4.1.conv1", 512, 512, 4, ("bn",), None),
+    ("layer1.x.conv1/2", 64, 64, 1, ("bn", "bn_add"), (7, 180, 320)),
+    ("layer2.x.conv1/2", 128, 128, 1, ("bn", "bn_add", "bn_bn_add"), (7, 90, 160)),
+]
+
 
 def timed(fn, launches):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -32,22 +47,76 @@ def timed(fn, launches):
     return a.elapsed_time(b) / launches
 
 
+def _bn(K, dev):
+    bn = nn.BatchNorm2d(K)
+    with torch.no_grad():
+        bn.running_mean.normal_(0, 0.3)
+        bn.running_var.uniform_(0.5, 1.5)
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.normal_(0, 0.3)
+    return bn.to(dev).eval()
+
+
+def epilogue_table(args, dev):
+    from mvdetr_amd.ops import conv_winograd as cw
+    from mvdetr_amd.ops.trunk_epilogue import bn_act
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    lines = [f"# convolution + epilogue (relu on), fp32 channel-last, ms over {args.launches} launches, {args.reps} interleaved "
+             "repetitions: (a) torch's convolution (MIOpen, cudnn.benchmark) + bn_act in place, (b) conv3x3_winograd_f32 + bn_act "
+             "in place, (c) conv3x3_winograd_f32 with the epilogue in its store",
+             "# shape               C->K     d  pixels       epilogue    (a) min/med/max          (b) min/med/max          "
+             "(c) min/med/max          c<b   c<a   c == b"]
+    for name, C, K, d, modes, pixels in EPILOGUE_SHAPES:
+        N, H, W = pixels or args.pixels
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last).eval()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        bn, bn2 = _bn(K, dev), _bn(K, dev)
+        res = torch.randn(N, K, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+        for mode in modes:
+            r, rbn = (None if mode == "bn" else res), (bn2 if mode == "bn_bn_add" else None)
+            side_a = lambda: bn_act(conv(x), bn, r, rbn, relu=True, inplace=True)  # noqa: E731
+            side_b = lambda: bn_act(cw.winograd_conv3x3(x, conv, force=True), bn, r, rbn, relu=True, inplace=True)  # noqa: E731
+            side_c = lambda: cw.winograd_conv3x3_bn_act(x, conv, bn, r, rbn, relu=True, force=True)  # noqa: E731
+            with torch.no_grad():
+                for _ in range(3):
+                    side_a()
+                    same = torch.equal(side_b(), side_c())
+                t = [[], [], []]
+                for _ in range(args.reps):
+                    for side, fn in zip(t, (side_a, side_b, side_c)):
+                        side.append(timed(fn, args.launches))
+            cols = "     ".join(f"{min(v):6.3f} {med(v):6.3f} {max(v):6.3f}" for v in t)
+            lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {mode + '_relu':<15} {cols}     "
+                         f"{sum(c < b for c, b in zip(t[2], t[1]))}/{args.reps}   {sum(c < a for c, a in zip(t[2], t[0]))}/{args.reps}   "
+                         f"{same}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--pixels", type=int, nargs=3, default=(7, 90, 160), metavar=("N", "H", "W"))
     ap.add_argument("--out")
+    ap.add_argument("--epilogue", action="store_true", help="time the convolutions with their epilogues, three sides")
     args = ap.parse_args()
     from mvdetr_amd.ops import conv_winograd as cw
     torch.backends.cudnn.benchmark = True
     dev = torch.device("cuda:0")
     N, H, W = args.pixels
-    lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, {N} x {H} x {W} pixels, fp32 channel-last, ms per launch "
-             f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",
-             "# shape               C->K     d  GFLOP   torch min/med/max        winograd min/med/max     TF/s(direct-equivalent)  "
-             "wins  err torch / winograd vs fp64"]
-    for name, C, K, d in SHAPES:
+    shapes = SHAPES
+    if args.epilogue:
+        lines, shapes = epilogue_table(args, dev), []
+    else:
+        lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, {N} x {H} x {W} pixels, fp32 channel-last, ms per launch "
+                 f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",
+                 "# shape               C->K     d  GFLOP   torch min/med/max        winograd min/med/max     TF/s(direct-equivalent)  "
+                 "wins  err torch / winograd vs fp64"]
+    for name, C, K, d in shapes:
         torch.manual_seed(C + K + d)
         conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
         nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
