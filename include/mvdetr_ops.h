@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel */
+#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel; still 18 with mvdetr_attn_forward_f16 / _bf16 and mvdetr_deform_conv2d_forward_f16 / _bf16 (purely additive) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -494,6 +494,29 @@ int mvdetr_deform_conv2d_backward_f64(void *stream, const double *grad_out, cons
                                       double *grad_weight);
 /* Name of the kernel route the last deformable-convolution call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_deform_conv2d_last_kernel(void);
+
+/* 16-bit inference forward (float16 / bfloat16 as raw 16-bit words; 16-bit storage, fp32 arithmetic, ONE rounding on the way
+ * out): "dc_fwd_mfma_half", the implicit GEMM of dc_fwd_mfma on v_mfma_f32_32x32x16_{f16,bf16} (csrc/deform_conv_half.hip).
+ *   input   channel-last memory [batch, in_h, in_w, in_channels] (input_nhwc must be 1), 16-byte aligned
+ *   offset  [batch, 2 * kernel_h * kernel_w, out_h, out_w] (offset_groups must be 1); positions are formed in fp32
+ *   weight  PERMUTED to [kernel_h * kernel_w][out_channels][in_channels], 16-byte aligned; bias [out_channels] or NULL
+ *   out     NCHW: element (b, o, h, w) at out[b * out_batch_stride + (o * out_h + h) * out_w + w]; out_batch_stride (in
+ *           elements) >= out_channels * out_h * out_w, so a channel slice of a larger [batch, N * C, h, w] tensor can be
+ *           written in place; relu != 0 applies max(., 0) before the rounding
+ * in_channels % 16 == 0 and out_channels % 32 == 0.  The entries validate before they touch the device and launch nothing
+ * they refuse: hipErrorInvalidValue for a bad shape or a null pointer, hipErrorNotSupported for offset_groups != 1,
+ * input_nhwc == 0, channel counts the kernel does not take or a misaligned pointer.  Every output element is owned by one
+ * lane: results are bit-reproducible run to run. */
+int mvdetr_deform_conv2d_forward_f16(void *stream, const uint16_t *input, const uint16_t *offset, const uint16_t *weight,
+                                     const uint16_t *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                     int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                     int dil_w, int offset_groups, int input_nhwc, int relu, int64_t out_batch_stride,
+                                     uint16_t *out);
+int mvdetr_deform_conv2d_forward_bf16(void *stream, const uint16_t *input, const uint16_t *offset, const uint16_t *weight,
+                                      const uint16_t *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                      int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                      int dil_w, int offset_groups, int input_nhwc, int relu, int64_t out_batch_stride,
+                                      uint16_t *out);
 
 /* ---- Fused multi-head attention (the op inside nn.MultiheadAttention; reference call sites models/transformer.py:40,59) ---
  *   out[b, h, i, :] = sum_j softmax_j(scale * q[b, h, i, :] . k[b, h, j, :]) * v[b, h, j, :],   scale = 1 / sqrt(head_dim)

@@ -31,6 +31,7 @@ _MSDA_FUSED_HALF = [_vp] * 5 + [ctypes.c_int64, _vp] + [_i] * 7 + [_vp]
 _MSDA_FUSED_LEVELS = [_vp] * 5 + [ctypes.c_int64] + [_vp] * 2 + [_i] * 12 + [_vp]
 _DC_FWD = [_vp] * 5 + [_i] * 15 + [_vp]
 _DC_BWD = [_vp] * 5 + [_i] * 15 + [_vp] * 3
+_DC_FWD_HALF = [_vp] * 5 + [_i] * 16 + [ctypes.c_int64, _vp]
 _i64p, _d, _u64 = ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_uint64
 _ATTN_FWD = [_vp] * 4 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 2
 _ATTN_BWD = [_vp] * 7 + [_i64p] + [_i] * 5 + [_d, _u64] + [_vp] * 4
@@ -131,6 +132,8 @@ SIGNATURES = {
     "mvdetr_deform_conv2d_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_deform_conv2d_forward_f32": (_DC_FWD, _i),
     "mvdetr_deform_conv2d_forward_f64": (_DC_FWD, _i),
+    "mvdetr_deform_conv2d_forward_f16": (_DC_FWD_HALF, _i),
+    "mvdetr_deform_conv2d_forward_bf16": (_DC_FWD_HALF, _i),
     "mvdetr_deform_conv2d_backward_f32": (_DC_BWD, _i),
     "mvdetr_deform_conv2d_backward_f64": (_DC_BWD, _i),
     "mvdetr_deform_conv2d_forward_host_f32": (_DC_FWD[1:], _i),

@@ -350,14 +350,16 @@ class MVDeTr(nn.Module):
         on the way out; so do the trunk's BatchNorm / ReLU / residual-add / max-pool epilogues (ops/trunk_epilogue.py:
         16-bit activations, the float32 BatchNorm vectors kept above; ``bn(x) + identity`` is not rounded in between).
         ``forward`` then returns 16-bit head maps; ``detect`` upcasts the two world maps for the detection extraction.
-        Served for the ``deform_trans``, ``conv`` and ``trans`` world features (``trans``: the encoder's attention core is the
-        16-bit MFMA kernel of csrc/attention_half.hip, which has no host path, so the model must be on a CUDA device when it
-        is converted); ``deform_conv`` is refused.  Training, ``torch.autocast`` and the backward are not part of it."""
+        Served for all four world features.  ``trans`` (its encoder's attention core is the 16-bit MFMA kernel of
+        csrc/attention_half.hip) and ``deform_conv`` (its deformable convolutions are dc_fwd_mfma_half of
+        csrc/deform_conv_half.hip) have no 16-bit host path: the model must be on a CUDA device when it is converted.
+        Training, ``torch.autocast`` and the backward are not part of it."""
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError("to_inference: dtype must be torch.float16 or torch.bfloat16")
-        if self.world_feat_arch == "deform_conv":
-            raise NotImplementedError("to_inference: the 'deform_conv' world feature's deformable convolution is float32 / "
-                                      "float64 only; 'deform_trans', 'conv' and 'trans' convert")
+        if self.world_feat_arch == "deform_conv" and not all(p.is_cuda for p in self.parameters()):
+            raise NotImplementedError("to_inference: the 'deform_conv' world feature's 16-bit deformable convolution is "
+                                      "GPU-only (there is no 16-bit host path): move the model to a CUDA device first, "
+                                      "then convert it")
         if self.world_feat_arch == "trans" and not all(p.is_cuda for p in self.parameters()):
             raise NotImplementedError("to_inference: the 'trans' world feature's 16-bit attention is GPU-only (there is no "
                                       "16-bit host path): move the model to a CUDA device first, then convert it")
@@ -370,6 +372,8 @@ class MVDeTr(nn.Module):
                     p.data = p.data.to(dtype)
             if hasattr(m, "cache_fused_projection"):
                 m._fused_cache = None                                      # (a cached permuted weight has the old dtype)
+            if hasattr(m, "_half_weight_cache"):
+                m._half_weight_cache = None                                # (DeformConv2d's permuted 16-bit weight likewise)
         for name in ("pos_embedding", "coord_map"):
             if name in self.world_feat._buffers and self.world_feat._buffers[name] is not None:
                 self.world_feat._buffers[name] = self.world_feat._buffers[name].to(dtype)

@@ -13,13 +13,23 @@ channel-last input (``torch.channels_last``, e.g. ``warp_perspective(..., channe
 offset group, C_in % 16 == 0 and C_out % 32 == 0 take the MFMA implicit GEMM; an NCHW input of that shape is transposed to
 channel-last first; everything else takes the generic kernels.  CPU tensors run the library's host path.  Gradients flow to
 input, offset, weight and bias; the backward is not bit-reproducible run to run (atomics), like torchvision's CUDA kernel.
-Not provided: the DCNv2 modulation ``mask`` and weight ``groups > 1`` (NotImplementedError), 16-bit dtypes (RuntimeError).
+
+16-bit inference (float16 / bfloat16 CUDA tensors of one dtype, forward only): a call of the MFMA shape (one offset group,
+C_in % 16 == 0, C_out % 32 == 0) runs ``dc_fwd_mfma_half`` of csrc/deform_conv_half.hip -- 16-bit storage, fp32 arithmetic,
+one rounding on the way out -- on a channel-last input read in place (an NCHW input is copied to channel-last first); the
+kernel takes the weight permuted to [kh * kw, C_out, C_in], one small copy per call that ``DeformConv2d`` caches in eval mode.
+Every other 16-bit CUDA call (odd channel counts, two offset groups, a data pointer that is not 16-byte aligned) is computed
+as ``deform_conv2d(x.float(), ...).to(dtype)`` on the fp32 routes above, and ``MVDETR_DEFORM_CONV_HALF=0`` (read per call)
+sends the kernel's calls there too.  A 16-bit call with a tensor that requires grad while grad is enabled raises: forward only.
+Not provided: the DCNv2 modulation ``mask`` and weight ``groups > 1`` (NotImplementedError), 16-bit CPU tensors (RuntimeError).
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -30,8 +40,8 @@ from .warp import _transpose
 
 
 def last_kernel() -> str:
-    """Route of the last deformable-convolution call of this process on the device: "dc_fwd_mfma", "dc_fwd_generic",
-    "dc_bwd_mfma" or "dc_bwd_generic" (tests / tools introspection)."""
+    """Route of the last deformable-convolution call of this process on the device: "dc_fwd_mfma", "dc_fwd_mfma_half",
+    "dc_fwd_generic", "dc_bwd_mfma" or "dc_bwd_generic" (tests / tools introspection)."""
     return _lib.lib().mvdetr_deform_conv2d_last_kernel().decode()
 
 
@@ -109,9 +119,69 @@ class DeformConv2dFunction(Function):
         return grad_input, grad_offset, grad_weight, grad_bias, None, None, None, None
 
 
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def permute_weight(weight):
+    """[C_out, C_in, kh, kw] -> the 16-bit kernel's [kh * kw, C_out, C_in] copy (a weight-tile row is one contiguous run)."""
+    Co, C, kh, kw = weight.shape
+    return weight.detach().permute(2, 3, 0, 1).reshape(kh * kw, Co, C).contiguous()
+
+
+def half_kernel_serves(input, weight, offset_groups):
+    """True when a 16-bit CUDA call of these shapes goes to dc_fwd_mfma_half (given an aligned or copied input)."""
+    C, Co = input.shape[1], weight.shape[0]
+    return (input.is_cuda and input.dtype in _HALF and offset_groups == 1 and C >= 16 and C % 16 == 0 and Co >= 32
+            and Co % 32 == 0 and Co <= 65535 * 128 and input.numel() > 0
+            and os.environ.get("MVDETR_DEFORM_CONV_HALF", "1") != "0")
+
+
+def _forward_half(input, offset, weight, bias, conf, relu=False, out=None, weight_t=None):
+    """The 16-bit CUDA forward: dc_fwd_mfma_half where it serves the call, else the fp32 routes on upcast tensors.  ``relu``
+    applies max(., 0) (in the kernel's store); ``out`` [B, C_out, H_out, W_out] may be a channel slice of a larger tensor."""
+    stride, padding, dilation, G = conf
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, weight, bias)):
+        raise RuntimeError("deform_conv2d: float16 / bfloat16 calls are forward-only (inference): a tensor requires grad; "
+                           "call under torch.no_grad() or use float32")
+    B, Co, (Ho, Wo) = input.shape[0], weight.shape[0], offset.shape[2:]
+    x, ok = input, half_kernel_serves(input, weight, G)
+    if ok:
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        ok = x.data_ptr() % 16 == 0
+    if ok and out is not None:
+        ok = (out.dtype == x.dtype and out.device == x.device and tuple(out.shape) == (B, Co, Ho, Wo)
+              and out.stride()[1:] == (Ho * Wo, Wo, 1) and (B == 1 or out.stride(0) >= Co * Ho * Wo))
+    if not ok:
+        res = deform_conv2d(input.float(), offset.float(), weight.float(), None if bias is None else bias.float(),
+                            stride, padding, dilation).to(input.dtype)
+        res = F.relu(res) if relu else res
+        return res if out is None else out.copy_(res)
+    offset = offset.contiguous()
+    if weight_t is None:
+        weight_t = permute_weight(weight)
+    bias = None if bias is None else bias.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
+    out_batch_stride = out.stride(0) if B > 1 else Co * Ho * Wo
+    args = _args(x, weight, conf) + [1, int(bool(relu)), out_batch_stride, out.data_ptr()]
+    with torch.cuda.device(x.device):
+        rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_forward_{_lib.suffix(x.dtype, half_ok=True)}")(
+            _lib.current_stream_ptr(x.device), x.data_ptr(), offset.data_ptr(), weight_t.data_ptr(),
+            None if bias is None else bias.data_ptr(), *args)
+    _lib.check(rc, "deform_conv2d_forward (16-bit)")
+    return out
+
+
 def deform_conv2d(input, offset, weight, bias=None, stride=1, padding=0, dilation=1, mask=None):
     """torchvision.ops.deform_conv2d (v1): input [B, C_in, H, W], offset [B, 2 * G * kh * kw, H_out, W_out], weight
     [C_out, C_in, kh, kw], bias [C_out] or None -> [B, C_out, H_out, W_out]."""
+    return _deform_conv2d(input, offset, weight, bias, stride, padding, dilation, mask)
+
+
+def _deform_conv2d(input, offset, weight, bias, stride, padding, dilation, mask, relu=False, out=None, weight_t=None):
+    """deform_conv2d; ``relu`` / ``out`` / ``weight_t`` are DeformConv2d's way into the 16-bit kernel's fused store and cached
+    permuted weight (16-bit CUDA calls only)."""
     if mask is not None:
         raise NotImplementedError("deform_conv2d: the DCNv2 modulation mask is not implemented")
     if input.dim() != 4 or offset.dim() != 4 or weight.dim() != 4:
@@ -123,7 +193,9 @@ def deform_conv2d(input, offset, weight, bias=None, stride=1, padding=0, dilatio
     dtypes = {t.dtype for t in (input, offset, weight, bias) if t is not None}
     if len(dtypes) != 1:
         raise RuntimeError(f"deform_conv2d: all tensors must have one dtype, got {sorted(map(str, dtypes))}")
-    _lib.suffix(input.dtype)                                       # 16-bit dtypes raise here
+    half = input.is_cuda and input.dtype in _HALF
+    if not half:
+        _lib.suffix(input.dtype)                                   # 16-bit CPU tensors raise here
     stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
     B, C, H, W = input.shape
     Co, Cw, kh, kw = weight.shape
@@ -150,6 +222,9 @@ def deform_conv2d(input, offset, weight, bias=None, stride=1, padding=0, dilatio
         raise RuntimeError(f"deform_conv2d: calculated output size {Ho}x{Wo} is too small")
     if tuple(offset.shape[2:]) != (Ho, Wo):
         raise RuntimeError(f"offset output dims: ({offset.shape[2]}, {offset.shape[3]}) - computed output dims: ({Ho}, {Wo})")
+    if half:
+        return _forward_half(input, offset, weight, bias, (stride, padding, dilation, G), relu=relu, out=out,
+                             weight_t=weight_t)
     return DeformConv2dFunction.apply(input, offset, weight, bias, stride, padding, dilation, G)
 
 
@@ -174,6 +249,7 @@ class DeformConv2d(nn.Module):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
+        self._half_weight_cache = None                          # (key, permuted 16-bit weight): _half_weight
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -183,9 +259,29 @@ class DeformConv2d(nn.Module):
             bound = 1 / math.sqrt(fan_in)
             nn.init.uniform_(self.bias, -bound, bound)
 
+    def _half_weight(self, input):
+        """The kernel's permuted copy of the weight for a 16-bit CUDA call in eval mode, cached until the weight is
+        replaced, written in place or cast (the key: its data_ptr, _version and dtype); None otherwise."""
+        w = self.weight
+        if self.training or not (input.is_cuda and input.dtype in _HALF and w.dtype == input.dtype and w.is_cuda):
+            return None
+        key = (w.data_ptr(), w._version, w.dtype)
+        if self._half_weight_cache is None or self._half_weight_cache[0] != key:
+            self._half_weight_cache = (key, permute_weight(w))
+        return self._half_weight_cache[1]
+
     def forward(self, input, offset, mask=None):
-        return deform_conv2d(input, offset, self.weight, self.bias, stride=self.stride, padding=self.padding,
-                             dilation=self.dilation, mask=mask)
+        return _deform_conv2d(input, offset, self.weight, self.bias, self.stride, self.padding, self.dilation, mask,
+                              weight_t=self._half_weight(input))
+
+    def forward_relu_into(self, input, offset, out):
+        """16-bit CUDA inference only: ``out.copy_(relu(self(input, offset)))`` where ``out`` may be a channel slice of a
+        larger [B, N * C_out, H_out, W_out] tensor; dc_fwd_mfma_half applies the ReLU in its store and writes the slice in
+        place.  The same bits as the composition."""
+        if not (input.is_cuda and input.dtype in _HALF):
+            raise RuntimeError("DeformConv2d.forward_relu_into serves float16 / bfloat16 CUDA tensors only")
+        return _deform_conv2d(input, offset, self.weight, self.bias, self.stride, self.padding, self.dilation, None,
+                              relu=True, out=out, weight_t=self._half_weight(input))
 
     def extra_repr(self) -> str:
         s = f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}"

@@ -255,7 +255,12 @@ class DeformConvWorldFeat(nn.Module):
     (the reference keeps it as a plain attribute), so a reference checkpoint loads with strict=True.
 
     The input may arrive channel-last ([B, N, H, W, C], straight from warp_perspective(..., channels_last_out=True)): each
-    camera's features are then read in place by the deformable convolution's channel-last kernel."""
+    camera's features are then read in place by the deformable convolution's channel-last kernel.
+
+    16-bit inference (float16 / bfloat16 CUDA input, eval mode, nothing requiring grad): the concatenated [B, N * C, H, W]
+    tensor is allocated once and each camera's deformable convolution (dc_fwd_mfma_half) writes its channel slice with the
+    ReLU applied in its store -- no ReLU passes and no ``torch.cat`` copy; the bits are those of the composition below.
+    fp32 / fp64 / CPU / training calls keep that composition."""
 
     def __init__(self, num_cam, Rworld_shape, base_dim, hidden_dim=128):
         super().__init__()
@@ -270,6 +275,17 @@ class DeformConvWorldFeat(nn.Module):
 
     def forward(self, x, visualize=False):
         channel_last = x.shape[2] != self.base_dim                    # [B, N, H, W, C]
+        if (x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and not self.training
+                and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            B, N = x.shape[:2]
+            H, W = x.shape[2:4] if channel_last else x.shape[3:5]
+            C = self.base_dim
+            cat = x.new_empty((B, N * C, H, W))
+            for n in range(N):
+                view = x[:, n].permute(0, 3, 1, 2) if channel_last else x[:, n]
+                feat = view + self.pos_embedding
+                self.deform_conv[n].forward_relu_into(feat, self.deform_pos[n](feat), cat[:, n * C:(n + 1) * C])
+            return self.world_feat(self.merge_linear(cat))
         feats = []
         for n in range(x.shape[1]):
             view = x[:, n].permute(0, 3, 1, 2) if channel_last else x[:, n]     # NCHW view (channel-last memory)

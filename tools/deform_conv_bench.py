@@ -5,9 +5,16 @@ per camera (conv_world_feat.py:55-76), forward and backward, for the Wildtrack (
 
     python tools/deform_conv_bench.py [--iters N] [--configs wildtrack,multiviewx,stress16]
 
+    python tools/deform_conv_bench.py --half-runs N      the 16-bit A/B only (below)
+
 Prints one JSON line per (config, implementation) and a table.  Times are device-event times of whole frames (all cameras)
 after warm-up; TF/s counts 2 * pixels * C_out * C_in * 9 FLOP per camera forward and twice that backward (g_col and grad_W)
-against the 157.3 TF fp32 MFMA peak."""
+against the 157.3 TF fp32 MFMA peak.
+
+--half-runs N: at the Wildtrack frame, per 16-bit dtype, the forward of dc_fwd_mfma_half (channel-last 16-bit input, the
+permuted weight cached as DeformConv2d caches it), of the fp32 dc_fwd_mfma on the same values (upcast once, outside the timing)
+and of the upcast fallback (MVDETR_DEFORM_CONV_HALF=0: the four .float() casts, dc_fwd_mfma, one .to(dtype)); the three are
+interleaved frame by frame in one session, each figure the median of 20 device-event frame times, N runs."""
 import argparse
 import json
 import os
@@ -97,14 +104,73 @@ def run(name, iters):
     return rows
 
 
+def half_ab(runs, frames=20):
+    from mvdetr_amd.ops import deform_conv
+    N, C, H, W = CONFIGS["wildtrack"]
+    dev = torch.device("cuda:0")
+    rows = []
+    for dtype in (torch.float16, torch.bfloat16):
+        g = torch.Generator().manual_seed(0)
+        cams = []
+        for _ in range(N):
+            x = torch.randn(1, C, H, W, generator=g).to(dev, dtype).contiguous(memory_format=torch.channels_last)
+            off = torch.randn(1, 18, H, W, generator=g).to(dev, dtype)
+            w = (torch.randn(C, C, 3, 3, generator=g) / (3 * C ** 0.5)).to(dev, dtype)
+            b = (torch.randn(C, generator=g) * 0.1).to(dev, dtype)
+            cams.append((x, off, w, b, deform_conv.permute_weight(w), [t.float() for t in (x, off, w, b)]))
+
+        def half():
+            for x, o, w, b, wt, _ in cams:
+                deform_conv._deform_conv2d(x, o, w, b, 1, 1, 1, None, weight_t=wt)
+
+        def fp32():
+            for *_, f in cams:
+                deform_conv.deform_conv2d(*f, padding=1)
+
+        def upcast():
+            os.environ["MVDETR_DEFORM_CONV_HALF"] = "0"
+            for x, o, w, b, _, _ in cams:
+                deform_conv.deform_conv2d(x, o, w, b, padding=1)
+            del os.environ["MVDETR_DEFORM_CONV_HALF"]
+        impls = {"dc_fwd_mfma_half": half, "dc_fwd_mfma_fp32_same_values": fp32, "upcast_fallback": upcast}
+        routes = {}
+        with torch.no_grad():
+            for name, fn in impls.items():
+                for _ in range(3):
+                    fn()
+                routes[name] = deform_conv.last_kernel()
+            torch.cuda.synchronize()
+            for run_ in range(runs):
+                times = {k: [] for k in impls}
+                for _ in range(frames):
+                    for name, fn in impls.items():
+                        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        start.record()
+                        fn()
+                        end.record()
+                        end.synchronize()
+                        times[name].append(start.elapsed_time(end) * 1e3)
+                row = {"ab": "deform_conv_half", "dtype": str(dtype), "run": run_, "cameras": N, "channels": C, "grid": [H, W],
+                       "median_of": frames, "last_kernel": routes}
+                for name, ts in times.items():
+                    row[name + "_us_per_frame"] = round(sorted(ts)[len(ts) // 2], 1)
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--half-runs", type=int, default=0)
     ap.add_argument("--configs", default="wildtrack,multiviewx,stress16")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("deform_conv_bench: needs a GPU (no CPU fallback for timings)")
     print(f"# device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {a.iters} frames per timing")
+    if a.half_runs:
+        half_ab(a.half_runs)
+        return
     rows = []
     for name in a.configs.split(","):
         rows += run(name, a.iters)

@@ -9,6 +9,8 @@ repetition by repetition (same call, alternating, spread first):
   add_layernorm   ops.add_layer_norm alone with the second output, 75,600 rows x 128;
   trans           a whole frame (MVDeTr.detect) of the ``trans`` world feature: the encoder's attention core is attn_fwd_mfma in
                   float32 and attn_fwd_mfma_half in 16 bits (models of its own, built only when the row is asked for);
+  deform_conv     a whole frame (MVDeTr.detect) of the ``deform_conv`` world feature: the per-camera deformable convolutions
+                  are dc_fwd_mfma in float32 and dc_fwd_mfma_half in 16 bits (models of its own, likewise);
 
 each for float32, bfloat16 and float16; then, for each 16-bit variant,
 
@@ -90,7 +92,7 @@ def detection_cells(model, imgs, M, thres):
     return set(det.cell[0, :min(n, det.cell.shape[1])].tolist())
 
 
-ROWS = ("detect", "hot_path", "warp", "msda", "add_layernorm", "trans", "trunk", "trunk_kernels", "detections")
+ROWS = ("detect", "hot_path", "warp", "msda", "add_layernorm", "trans", "deform_conv", "trunk", "trunk_kernels", "detections")
 
 
 def trunk_kernel_launches(views, feat_hw, dtype, device):
@@ -202,6 +204,16 @@ def main():
                 fns["trans"][name] = lambda m=m: m.detect(imgs, M)
                 fns["trans"][name]()
                 kernels["trans"][name] = f"{warp_mod.last_kernel()} + {attn_last_kernel()}"
+
+        if "deform_conv" in only:
+            from mvdetr_amd.ops.deform_conv import last_kernel as dc_last_kernel
+            fns["deform_conv"], kernels["deform_conv"] = {}, {}
+            for name, dtype in VARIANTS.items():
+                m = build_model(a.config, seed=0, world_feat_arch="deform_conv").to(DEV).eval()
+                m = m if dtype is None else m.to_inference(dtype)
+                fns["deform_conv"][name] = lambda m=m: m.detect(imgs, M)
+                fns["deform_conv"][name]()
+                kernels["deform_conv"][name] = f"{warp_mod.last_kernel()} + {dc_last_kernel()}"
 
         rows = []
         for what, variants in fns.items():
