@@ -400,6 +400,10 @@ const char *mvdetr_winograd_last_kernel(void);
  * (mvdetr_trunk_last_kernel's names). */
 const char *mvdetr_winograd_last_epilogue(void);
 int64_t mvdetr_winograd_launch_count(void);
+/* The convolution's grid is persistent: min(units, CUs) workgroups, each running every G-th unit of 64 tiles x 64 output
+ * channels.  This caps it at n workgroups for the whole process (0: no cap, the default) and returns the previous cap
+ * (additive entry).  For tests, so that small shapes run many units per workgroup; results do not depend on it. */
+int mvdetr_winograd_set_max_workgroups(int n);
 
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------
  * Name of the kernel variant the last forward call ON THIS THREAD dispatched to

@@ -106,6 +106,7 @@ SIGNATURES = {
     "mvdetr_winograd_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_winograd_last_epilogue": ([], ctypes.c_char_p),
     "mvdetr_winograd_launch_count": ([], ctypes.c_int64),
+    "mvdetr_winograd_set_max_workgroups": ([_i], _i),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f64": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f16": (_WARP, _i),

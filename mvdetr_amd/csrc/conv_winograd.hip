@@ -7,11 +7,17 @@
 // (p = 4 xi + nu, the position inside the 4x4 transformed tile): 2.25x fewer multiplications than the direct form.
 //
 //   winograd_weights_f32   U[p][c][k] = (G g G^T)[xi][nu], formed in fp64 and rounded once; runs once per weight tensor.
-//   conv3x3_winograd_f32   one launch: a workgroup of 4 waves owns 64 tiles x 64 output channels x all 16 positions.
+//   conv3x3_winograd_f32   one launch: a unit of work is 64 tiles x 64 output channels x all 16 positions, run by a workgroup
+//                          of 4 waves.
+//       * the grid is persistent: G = min(units, CUs) workgroups (131 KB of LDS: one per CU), workgroup g runs the units
+//         g, g + G, ... in that order -- no counter, no atomics.  Its chunk pipeline runs through all of them: the staging
+//         side, two chunks ahead, has its own (unit, chunk) cursor, so the input loads and LDS-DMA of a unit's first chunks
+//         are in flight while the unit before it is stored, and only the first unit pays a cold prologue;
 //       * every wave owns a 32-tile x 32-channel block of ALL sixteen products: 16 accumulators of v_mfma_f32_32x32x2_f32 =
 //         256 registers per lane (one wave per SIMD; the fp32 MFMA reaches its issue rate from one wave with independent
 //         accumulators), so A^T M A happens in registers -- position p of a (tile, channel) sits in the same lane and
-//         register of accumulator p -- and nothing but the result is ever stored;
+//         register of accumulator p -- and nothing but the result is ever stored.  A unit's first MFMA per position has a
+//         zero C operand, so nothing is cleared, and the store reads each accumulator register exactly once;
 //       * the input channels go by in chunks of 8: B^T d B is formed on the way into LDS (each lane transforms two channels
 //         of one tile from 16 8-byte loads), the U slice of the chunk is staged beside it; two LDS buffers, one barrier per
 //         chunk.  With one wave per SIMD every instruction that is not an MFMA costs its issue slots in full (measured:
@@ -27,12 +33,14 @@
 #include "../../include/mvdetr_ops.h"
 
 #include <atomic>
+#include <type_traits>
 
 namespace mvdetr {
 
 static std::atomic<const char *> g_winograd_last_kernel{"none"};
 static std::atomic<const char *> g_winograd_last_epilogue{"none"};
 static std::atomic<int64_t> g_winograd_launches{0};
+static std::atomic<int> g_winograd_max_workgroups{0};                         // 0: one per CU (mvdetr_winograd_set_max_workgroups)
 
 namespace wino {
 
@@ -46,7 +54,8 @@ constexpr int VROW = TILES;                // floats per (position, channel) row
 constexpr int V_FLOATS = 16 * CC * VROW;   // 8,192
 constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
 constexpr int BUF_FLOATS = V_FLOATS + U_FLOATS;
-constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TILES * 8;      // two buffers + the tiles' output descriptors = 131,584
+constexpr int TINFO_SLOTS = 4;             // units whose tiles' output descriptors are kept at a time (a power of two)
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 8;       // two buffers + the descriptors = 133,120
 
 // Range of the x buffer resource and the offset of a pixel outside the image (beyond it: the load returns zero)
 constexpr unsigned X_RANGE = 0xFFFFFFF0u, X_OUTSIDE = 0xFFFFFFF8u;
@@ -58,6 +67,7 @@ struct Shape {
     int th, tw;                            // tile grid of one sub-lattice
     unsigned tiles;                        // N * d * d * th * tw
     int kblocks;                           // K / 64
+    unsigned units;                        // ceil(tiles / 64) * kblocks: 64 tiles x 64 output channels each
 };
 
 // Where tile `t` sits: image, top-left OUTPUT pixel (y0, x0); false past the last tile.
@@ -92,63 +102,85 @@ template <int MODE, bool RELU>
 __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restrict__ x, const float *__restrict__ U,
                                                             float *__restrict__ y, const Shape s, const Epilogue ep)
 {
-    // ONE shared array: two {V, U} buffers, then the tiles' output descriptors {pixel offset from the workgroup's first
+    // ONE shared array: two {V, U} buffers, then four units' tiles' output descriptors {pixel offset from the unit's first
     // image, flags}
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int *const tinfo = reinterpret_cast<int *>(lds + 2 * BUF_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               // uniform: LDS-DMA targets by scalar arithmetic
-    // workgroups that share a 64-channel slice of U are 'kblocks' apart: with 8 (or 4, 2, 1) slices, consecutive ids being
-    // dealt round-robin over the 8 XCDs, each XCD's L2 serves one slice
-    const int kb = blockIdx.x % s.kblocks;
-    const unsigned tb = blockIdx.x / s.kblocks;
     const int C = s.C, K = s.K, d = s.d, H = s.H, W = s.W;
+    const int chunks = C / CC;
+    // The grid is persistent: workgroup g runs the units g, g + G, g + 2 G, ... (G = gridDim.x <= s.units), a unit being
+    // what a workgroup used to be.  Units that share a 64-channel slice of U are 'kblocks' apart: with 8 (or 4, 2, 1)
+    // slices, consecutive ids being dealt round-robin over the 8 XCDs, each XCD's L2 serves one slice, and with G a
+    // multiple of kblocks a workgroup keeps its slice -- which nothing below relies on.
+    const unsigned G = gridDim.x;
 
-    // every per-lane offset below is 32-bit and relative to the image of the workgroup's first tile (the host bounds the
-    // span of one workgroup's 64 tiles)
-    int n0, uy, ux;
-    tile_origin(s, tb * TILES, n0, uy, ux);
-    const float *const xblk = x + (size_t)n0 * H * W * C;
-    float *const yblk = y + (size_t)n0 * H * W * K + kb * KB;
-
-    // ---- the loader's tile: lane group of 4 = one tile, its 4 channel pairs --------------------------------------------------
+    // ---- the staging side: the unit and chunk whose loads are issued next ---------------------------------------------------
+    // Every per-lane offset is 32-bit and relative to the image of the unit's first tile (the host bounds the span of one
+    // unit's 64 tiles).  The loader's tile: lane group of 4 = one tile, its 4 channel pairs.
     const int ltile = tid >> 2, cp = tid & 3;
-    int n, y0, x0;
-    const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
     unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel pair cp
+    __amdgpu_buffer_rsrc_t xrsrc;                                             // the unit's image block, in SGPRs
+    const char *ublk;                                                         // the unit's 64-channel slice of U
+    // Entering unit u: its offsets, bases, and the output descriptors of its tiles into slot 'slot' of tinfo.  The staging
+    // side is at most two units ahead of the one whose store reads its slot (C = 8: one chunk per unit), and a barrier lies
+    // between any store and the write that is four units later: four slots.
+    auto enter_unit = [&](unsigned u, int slot) {
+        const int kb = (int)(u % (unsigned)s.kblocks);
+        const unsigned tb = u / (unsigned)s.kblocks;
+        int n0, uy, ux;
+        tile_origin(s, tb * TILES, n0, uy, ux);
+        xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)n0 * H * W * C), 0, (int)X_RANGE, 0x00020000);
+        ublk = reinterpret_cast<const char *>(U + kb * KB);
+        int n, y0, x0;
+        const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = y0 + (i - 1) * d, xx = x0 + (j - 1) * d;
-            const bool ok = tvalid && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : X_OUTSIDE;
+            for (int j = 0; j < 4; ++j) {
+                const int yy = y0 + (i - 1) * d, xx = x0 + (j - 1) * d;
+                const bool ok = tvalid & (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W);     // selects, not branches
+                off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : X_OUTSIDE;
+            }
         }
-    }
-
-    if (tid < TILES) {
-        int tn, ty0, tx0;
-        const bool ok = tile_origin(s, tb * TILES + tid, tn, ty0, tx0);
-        int flags = 0;
-        // a sub-lattice smaller than the largest one has tiles that start outside the image
-        if (ok && ty0 < H && tx0 < W) flags = 1 | (tx0 + d < W ? 2 : 0) | (ty0 + d < H ? 4 : 0);
-        tinfo[2 * tid + 0] = (int)((((unsigned)(tn - n0) * H + ty0) * W + tx0) * (unsigned)K);
-        tinfo[2 * tid + 1] = flags;
-    }
+        if (tid < TILES) {
+            int tn, ty0, tx0;
+            const bool ok = tile_origin(s, tb * TILES + tid, tn, ty0, tx0);
+            int flags = 0;
+            // a sub-lattice smaller than the largest one has tiles that start outside the image
+            if (ok && ty0 < H && tx0 < W) flags = 1 | (tx0 + d < W ? 2 : 0) | (ty0 + d < H ? 4 : 0);
+            int *const ti = tinfo + slot * (2 * TILES);
+            ti[2 * tid + 0] = (int)((((unsigned)(tn - n0) * H + ty0) * W + tx0) * (unsigned)K);
+            ti[2 * tid + 1] = flags;
+        }
+    };
+    unsigned su = blockIdx.x;                                                 // staging cursor: unit, its ordinal & 3, chunk
+    int sslot = 0, sc = 0;
+    // One position further in the workgroup's (unit, chunk) sequence; past its end the last chunk is staged again, into
+    // buffers nobody reads.  All of it is uniform: scalar arithmetic and one uniform branch.
+    auto advance = [&] {
+        if (sc + 1 < chunks) {
+            ++sc;
+        } else if (su + G < s.units) {
+            su += G;
+            sslot = (sslot + 1) & (TINFO_SLOTS - 1);
+            sc = 0;
+            enter_unit(su, sslot);
+        }
+    };
+    enter_unit(su, 0);
 
     // ---- U staging by LDS-DMA: the chunk's [16][8][64] slice is 8 x 16 bytes per lane, LDS image in lane order ---------------
     // float index f = r * 1024 + tid * 4 of the image [p][c][k]:  p = 2 r + (tid >> 7), c = (tid >> 4) & 7, k = (tid & 15) * 4
     const unsigned uoff = ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + (tid & 15) * 4) * 4u;   // bytes
-    const char *const ublk = reinterpret_cast<const char *>(U + kb * KB);
     const size_t ustep = (size_t)2 * C * K * 4;                               // two positions further per r, bytes
 
     // The x loads are raw buffer loads: the uniform base (image block + chunk) travels in SGPRs, the lane's 32-bit byte
     // offset in one VGPR, and a pixel outside the image has an offset past the buffer's range, for which the hardware
     // returns zero -- no per-lane 64-bit addresses, no selects.  (Valid offsets end below 2^32 - 64: the host's bound.)
     float2 raw[16];
-    const __amdgpu_buffer_rsrc_t xrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(xblk), 0, (int)X_RANGE, 0x00020000);
     auto load_x = [&](int c0, int e) {
         const auto v = __builtin_amdgcn_raw_buffer_load_b64(xrsrc, (int)off[e], c0 * 4, 0);
         static_assert(sizeof(v) == 8, "two floats");
@@ -220,9 +252,8 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     };
     auto mfma = [&](int p, int par) { acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[par][p], fb[par][p], acc[p], 0, 0, 0); };
 
-    const int chunks = C / CC;
-
-    // prologue: chunk 0 into buffer 0; then chunk 1's loads, and the operands of chunk 0's first k-step
+    // prologue: the first position (unit, chunk 0) into buffer 0; then the second position's loads, and the operands of the
+    // first k-step
     {
 #pragma unroll
         for (int q = 0; q < 16; ++q) load_piece(0, lds + V_FLOATS, q);
@@ -230,11 +261,11 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         for (int u = 0; u < 24; ++u) xform_piece(lds, u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this wave's LDS-DMA has landed
         __syncthreads();
-        const int c1 = (1 < chunks ? 1 : 0) * CC;
+        advance();
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             read_piece(lds, 0, q);
-            load_piece(c1, lds + BUF_FLOATS + V_FLOATS, q);
+            load_piece(sc * CC, lds + BUF_FLOATS + V_FLOATS, q);
         }
     }
 
@@ -246,20 +277,26 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     //   k-step 2   the second half
     //   barrier    every wave's V writes and LDS-DMA of the next chunk are done, all reads of this chunk are done
     //   k-step 3   its reads are the NEXT chunk's k-step 0; the loads of the chunk after it, into the buffer this chunk left
-    // No branch in the loop: past the last chunk the loads stage the last chunk again, into buffers nobody reads.
-    __builtin_amdgcn_sched_barrier(0);                                        // the 256 zeros are not live over the prologue
-#pragma unroll
-    for (int p = 0; p < 16; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-    int ch = 0;                                                               // the host refuses C < 8: at least one chunk
-    do {
-        float *const cur = lds + (ch & 1) * BUF_FLOATS;
-        float *const nxt = lds + ((ch & 1) ^ 1) * BUF_FLOATS;
+    // The loop runs over the positions (unit, chunk) of ALL the workgroup's units, and the staging side, two positions
+    // ahead, has a cursor of its own: the last chunks of a unit issue the x loads and the LDS-DMA of the next unit's first
+    // chunks, which fly over the stores between the two.  The k-steps carry no branch: the two uniform ones, the staging
+    // side entering a unit and the store behind a unit's last chunk, sit at the top and at the bottom of an iteration.
+    // A unit's first chunk is a copy of the chunk whose k-step 0 has a zero C operand: the accumulators are not live from
+    // one unit to the next, and nothing is cleared.
+    const int kcol = wn * 32 + (lane & 31);                                   // the lane stores ONE output channel of a unit
+    float bs = 1.f, bt = 0.f, bs2 = 0.f;                                      // its folded BatchNorm constants ...
+    int kb_folded = -1;                                                       // ... which are those of this channel block
+    unsigned cu = blockIdx.x;                                                 // compute cursor: unit, its ordinal & 3,
+    int cslot = 0, par = 0;                                                   // and the LDS buffer the position is in
+    auto chunk = [&](auto first) {
+        advance();
+        float *const cur = lds + par * BUF_FLOATS;
+        float *const nxt = lds + (par ^ 1) * BUF_FLOATS;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
-            mfma(p, 0);
+            if (decltype(first)::value) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0][p], fb[0][p], f32x16{}, 0, 0, 0);
+            else mfma(p, 0);
             read_piece(cur, 1, p);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -279,87 +316,124 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const int c2 = (ch + 2 < chunks ? ch + 2 : chunks - 1) * CC;
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
             mfma(p, 1);
             read_piece(nxt, 0, p);
-            load_piece(c2, cur + V_FLOATS, p);
+            load_piece(sc * CC, cur + V_FLOATS, p);
             __builtin_amdgcn_sched_barrier(0);
         }
-    } while (++ch < chunks);
-    // the loads of the last k-step 3 are nobody's, but an LDS-DMA must not outlive the workgroup's LDS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        par ^= 1;
+    };
+    do {
+        chunk(std::true_type{});
+        if (chunks > 1) {                                                     // (a zero-trip `for` has the allocator spill)
+            int ch = 1;
+            do chunk(std::false_type{});
+            while (++ch < chunks);
+        }
 
-    // ---- A^T M A in registers, then the stores ------------------------------------------------------------------------------------
-    const int kcol = wn * 32 + (lane & 31);
-    // The lane stores ONE output channel, kb * 64 + kcol: its BatchNorm constants, folded here on every call.
-    float bs = 1.f, bt = 0.f, bs2 = 0.f;
-    if (MODE >= 1) bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
-    if (MODE == 3) {
-        float bt2;
-        bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
-        bt = bt + bt2;
-    }
-    // The residual: every value this lane will add, 4 per accumulator register, requested before the first one is used --
-    // the loop's operand registers are dead, and with one workgroup per CU nothing else would hide a latency per register.
-    // Raw buffer loads as for x: the byte offsets of the stores below, and an element that is not stored gets an offset
-    // past the buffer's range, for which nothing is read.  The range ends with the tensor.
-    float q[16][4];
-    if (MODE >= 2) {
-        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
-        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, (int)(left < X_RANGE ? (unsigned)left : X_RANGE),
-            0x00020000);
-        const unsigned dx = (unsigned)d * K * 4u, dy = (unsigned)d * W * K * 4u;
+        // ---- behind the unit's last chunk: A^T M A in registers, then the stores -------------------------------------------------
+        // The operands of the next position's first k-step are already in registers and its loads in flight.
+        const int kb = (int)(cu % (unsigned)s.kblocks);
+        int n0, uy, ux;
+        tile_origin(s, cu / (unsigned)s.kblocks * TILES, n0, uy, ux);
+        float *const yblk = y + (size_t)n0 * H * W * K + kb * KB;
+        const int *const ti = tinfo + cslot * (2 * TILES);
+        // The BatchNorm constants of channel kb * 64 + kcol, folded when the workgroup's channel block changes: once per
+        // launch where the grid is a multiple of kblocks.
+        if (MODE >= 1 && kb != kb_folded) {
+            bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
+            if (MODE == 3) {
+                float bt2;
+                bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
+                bt = bt + bt2;
+            }
+            kb_folded = kb;
+        }
+        // The residual: 4 values per accumulator register, requested four registers' worth at a time and one such batch
+        // ahead of its use (the staged chunk and the next unit's offsets are live here: no room for all 64 at once).  Raw
+        // buffer loads as for x: the byte offsets of the stores below, and an element that is not stored gets an offset
+        // past the buffer's range, for which nothing is read.  The range ends with the tensor.
+        float q[2][4][4];
+        __amdgpu_buffer_rsrc_t rrsrc;
+        if (MODE >= 2) {
+            const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0,
+                                                      (int)(left < X_RANGE ? (unsigned)left : X_RANGE), 0x00020000);
+        }
+        auto load_res = [&](int b) {
+            const unsigned dx = (unsigned)d * K * 4u, dy = (unsigned)d * W * K * 4u;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int r = 4 * b + rr;
+                const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int flags = ti[2 * t + 1];
+                const unsigned o = ((unsigned)ti[2 * t + 0] + kcol) * 4u;
+                const unsigned o4[4] = {(flags & 1) ? o : X_OUTSIDE, (flags & 3) == 3 ? o + dx : X_OUTSIDE,
+                                        (flags & 5) == 5 ? o + dy : X_OUTSIDE, (flags & 7) == 7 ? o + dy + dx : X_OUTSIDE};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    q[b & 1][rr][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
+            }
+        };
+        if (MODE >= 2) {
+            load_res(0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // The accumulator reads below are written out by hand, so the wait states between the last MFMA's write and a
+        // read of its registers are too: 18 for a 16-pass MFMA, whatever the compiler puts between the two.
+        asm volatile("s_nop 15\n\ts_nop 3");
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const int flags = tinfo[2 * t + 1];
-            const unsigned o = ((unsigned)tinfo[2 * t + 0] + kcol) * 4u;
-            const unsigned o4[4] = {(flags & 1) ? o : X_OUTSIDE, (flags & 3) == 3 ? o + dx : X_OUTSIDE,
-                                    (flags & 5) == 5 ? o + dy : X_OUTSIDE, (flags & 7) == 7 ? o + dy + dx : X_OUTSIDE};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                q[r][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
-        }
-        __builtin_amdgcn_sched_barrier(0);                                    // all of them are issued ahead of the first store
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);     // the accumulator's row = the tile
-        const int flags = tinfo[2 * t + 1];
-        const unsigned pix = (unsigned)tinfo[2 * t + 0];
-        float s0[4], s1[4];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            s0[nu] = acc[nu][r] + acc[4 + nu][r] + acc[8 + nu][r];
-            s1[nu] = acc[4 + nu][r] - acc[8 + nu][r] - acc[12 + nu][r];
-        }
-        float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
-        float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
-        if (MODE >= 1) {
-            constexpr int RES = MODE - 1;
-            y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? q[r][0] : 0.f, bs2);
-            y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? q[r][1] : 0.f, bs2);
-            y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? q[r][2] : 0.f, bs2);
-            y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? q[r][3] : 0.f, bs2);
-        }
-        float *const o = yblk + pix + kcol;
-        if (flags & 1) {
-            o[0] = y00;
-            if (flags & 2) o[(size_t)d * K] = y01;
-            if (flags & 4) {
-                o[(size_t)d * W * K] = y10;
-                if (flags & 2) o[(size_t)d * W * K + (size_t)d * K] = y11;
+            if (MODE >= 2 && r % 4 == 0 && r + 4 < 16) {
+                load_res(r / 4 + 1);
+                __builtin_amdgcn_sched_barrier(0);                            // issued ahead of the stores of batch r / 4
             }
-        }
-        // one register's sixteen reads at a time, and the accumulators stay where the MFMAs left them: copied out all at
-        // once they take the whole VGPR file, and the allocator then spills the loop's operands to make room
+            const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); // the accumulator's row = the tile
+            const int flags = ti[2 * t + 1];
+            const unsigned pix = (unsigned)ti[2 * t + 0];
+            // Register r of the sixteen accumulators, read one by one: left to the compiler, an element of an accumulator
+            // costs a copy of all its sixteen registers, 4,096 reads per unit where 256 are needed.
+            float m[16];
 #pragma unroll
-        for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p]));
-        __builtin_amdgcn_sched_barrier(0);
-    }
+            for (int p = 0; p < 16; ++p) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[p]) : "a"(acc[p][r]));
+            float s0[4], s1[4];
+#pragma unroll
+            for (int nu = 0; nu < 4; ++nu) {
+                s0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
+                s1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
+            }
+            float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+            float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+            if (MODE >= 1) {
+                constexpr int RES = MODE - 1;
+                const float *const qr = q[(r >> 2) & 1][r & 3];
+                y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? qr[0] : 0.f, bs2);
+                y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? qr[1] : 0.f, bs2);
+                y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? qr[2] : 0.f, bs2);
+                y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? qr[3] : 0.f, bs2);
+            }
+            float *const o = yblk + pix + kcol;
+            if (flags & 1) {
+                o[0] = y00;
+                if (flags & 2) o[(size_t)d * K] = y01;
+                if (flags & 4) {
+                    o[(size_t)d * W * K] = y10;
+                    if (flags & 2) o[(size_t)d * W * K + (size_t)d * K] = y11;
+                }
+            }
+            // one register's sixteen reads at a time, and the accumulators stay where the MFMAs left them: copied out all at
+            // once they take the whole VGPR file, and the allocator then spills the loop's operands to make room
+#pragma unroll
+            for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        cu += G;
+        cslot = (cslot + 1) & (TINFO_SLOTS - 1);
+    } while (cu < s.units);
+    // the loads of the last k-step 3 are nobody's, but an LDS-DMA must not outlive the workgroup's LDS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // U[p = 4 xi + nu][c][k] = (G g G^T)[xi][nu] of weight[k][c][3][3], in fp64, rounded once.  One thread per (c, k).
@@ -439,8 +513,19 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     const int64_t blocks = (tiles + TILES - 1) / TILES * s.kblocks;
     if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
     s.tiles = (unsigned)tiles;
+    s.units = (unsigned)blocks;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const unsigned nb = (unsigned)blocks;
+    // the persistent grid: one workgroup per CU (one fits), each running every G-th unit; fewer under the tests' cap
+    static PerDevice<int> cus_of;
+    const int cus = cus_of.get([] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    });
+    const int cap = g_winograd_max_workgroups.load();
+    unsigned nb = s.units < (unsigned)cus ? s.units : (unsigned)cus;
+    if (cap > 0 && nb > (unsigned)cap) nb = (unsigned)cap;
     int rc;
     if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep);
     else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep) : launch<1, false>(st, nb, x, U, y, s, ep);
@@ -493,3 +578,5 @@ extern "C" const char *mvdetr_winograd_last_kernel(void) { return mvdetr::g_wino
 extern "C" const char *mvdetr_winograd_last_epilogue(void) { return mvdetr::g_winograd_last_epilogue.load(); }
 
 extern "C" int64_t mvdetr_winograd_launch_count(void) { return mvdetr::g_winograd_launches.load(); }
+
+extern "C" int mvdetr_winograd_set_max_workgroups(int n) { return mvdetr::g_winograd_max_workgroups.exchange(n > 0 ? n : 0); }

@@ -82,17 +82,18 @@ __global__ __launch_bounds__(256) void bn_act_cl_any(const float *x, BnVectors b
     const int cg = C >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (int64_t)gridDim.x * 256) {
         const int col = (int)(i % cg);
-        float4 s, t;
+        float4 s, t, s2;
         bn_fold4(bn, col * 4, s, t);
+        if (MODE == 2) {                                                        // t + t2 first, as in bn_act_cl: one arithmetic
+            float4 t2;
+            bn_fold4(bn2, col * 4, s2, t2);
+            t = make_float4(t.x + t2.x, t.y + t2.y, t.z + t2.z, t.w + t2.w);
+        }
         float4 z = fma4(*reinterpret_cast<const float4 *>(x + i * 4), s, t);
         if (MODE) {
             const float4 q = *reinterpret_cast<const float4 *>(r + i * 4);
             if (MODE == 1) z = make_float4(z.x + q.x, z.y + q.y, z.z + q.z, z.w + q.w);
-            if (MODE == 2) {
-                float4 s2, t2;
-                bn_fold4(bn2, col * 4, s2, t2);
-                z = fma4(q, s2, make_float4(z.x + t2.x, z.y + t2.y, z.z + t2.z, z.w + t2.w));
-            }
+            if (MODE == 2) z = fma4(q, s2, z);
         }
         if (RELU) z = make_float4(relu_nan(z.x), relu_nan(z.y), relu_nan(z.z), relu_nan(z.w));
         *reinterpret_cast<float4 *>(y + i * 4) = z;

@@ -89,6 +89,12 @@ def launch_count() -> int:
     return int(_lib.lib().mvdetr_winograd_launch_count())
 
 
+def set_winograd_max_workgroups(n: int) -> int:
+    """Cap the convolution's persistent grid at ``n`` workgroups for this process (0: the default, one per CU); returns
+    the previous cap.  For tests, so that small shapes run many units per workgroup; results do not depend on it."""
+    return int(_lib.lib().mvdetr_winograd_set_max_workgroups(int(n)))
+
+
 def _on_device(t) -> bool:
     return t.is_cuda
 
