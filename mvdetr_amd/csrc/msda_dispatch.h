@@ -3,10 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "msda_backward_route.h"
+#include "msda_forward_route.h"
+#include "msda_tile.h"
 
 namespace mvdetr {
-
-enum class MsdaFwdImpl { Gather, Tile };
 
 // name of the kernel the last forward on this thread launched (bench / tests only; set by the launchers)
 // what the code object says about a kernel (hipFuncGetAttributes): registers per lane, scratch (spill) bytes per lane,
@@ -23,30 +23,43 @@ inline KernelResources kernel_resources(const void *func)
 }
 void msda_note_forward_kernel(const char *name, const KernelResources *res = nullptr);
 
-// fp32 LDS-tiled encoder kernel (msda_forward_tile.hip).  Only valid when
-// msda_fwd_choose_impl() returned Tile.
-// local_hits: device counter written by msda_launch_locality_probe (or NULL: no probe)
-int msda_forward_tile(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                      const float *loc, const float *aw, int B, int S, int M, int D, int L, int Lq,
-                      int P, float *out, const int *local_hits);
-// false when the kernel that takes the call decides per tile, inside the launch, whether to stage windows (msda_fwd_group2)
-bool msda_forward_tile_wants_probe(int B, int S, int M, int D, int L);
-inline int msda_forward_tile(hipStream_t, const double *, const int64_t *, const int64_t *,
-                             const double *, const double *, int, int, int, int, int, int, int,
-                             double *, const int *)
-{
-    return 1;  // never chosen for fp64
-}
+// options of a camera-grouped launch (MsdaFwdCall::opts, the kernels' `opts` argument)
+#define GROUP_OPT_NO_SHIFT 1      // keep the windows centred on the tile (A/B knob MVDETR_MSDA_WINDOW_SHIFT=0)
+#define GROUP_OPT_BLOCKS 2        // XCD k takes a 2-D block of the tile grid instead of a band of the job list
+#define GROUP_OPT_STANDDOWN 4     // (msda_fwd_group2, public contract) a job whose taps are far from its cells gathers instead
 
-// MVDETR_MSDA_FWD_IMPL = auto (default) | gather | tile; overridable at run time through
-// mvdetr_msda_set_forward_impl().
-int msda_fwd_impl_knob();
+// One fp32 forward call as every launcher below receives it (host only, never a kernel parameter).  The public and the fused
+// contract share the kernels' argument slots: loc / aw hold final sampling locations and attention weights (ref_mode 0, ref
+// unused), or the raw offsets and logits next to reference points [.., Lq, L, P, 2] (ref_mode 1) or one reference point per
+// (query, level) (ref_mode 2).  stats: where the training entry wants its softmax statistics, or null.  probe:
+// msda_launch_locality_probe's scratch, or null (no probe)
+struct MsdaFwdCall {
+    hipStream_t st;
+    const float *value;
+    const int64_t *shapes, *lsi;
+    const float *loc, *aw;
+    const float *ref;
+    int64_t ref_bstride;
+    SamplingLayout lay;
+    QueryLevels qr;
+    int ref_mode;
+    int B, S, M, D, L;
+    float *out, *stats;
+    const int *probe;
+    int opts;
+};
 
-// fused variant: reference points + raw offsets + raw logits (see msda_forward_tile.hip)
-int msda_forward_tile_fused(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                            const float *ref, int64_t ref_bstride, const float *offsets, const float *logits,
-                            int layout, int qstride_l, int qstride_w, int ql0, int ql1, int Lq, int B, int S,
-                            int M, int D, int L, float *out, float *stats = nullptr);
+// The launchers of msda_forward_route.h's routes; which of them a call takes is decided there, they only pick the instantiation
+// from D, L and ref_mode.
+// LDS-tiled encoder kernel (msda_forward_tile.hip)
+int msda_forward_tile(const MsdaFwdCall &c);
+// camera-grouped kernels: 6 / 7 cameras, software-pipelined (msda_forward_group.hip); 9..16 cameras, 4 lane groups x up to 4
+// cameras (msda_forward_group_many.hip)
+int msda_forward_group2(const MsdaFwdCall &c);
+int msda_forward_group_many(const MsdaFwdCall &c);
+// the fused training forward's statistics -- (maximum, 1 / sum exp) of a (query, head)'s L x P logits -- for calls whose forward
+// kernel does not write them itself (the camera-grouped kernels do): msda_forward_tile.hip
+int msda_softmax_stats(hipStream_t st, const float *logits, SamplingLayout lay, int64_t queries, int M, int L, float *stats);
 
 // One backward call as every launcher below receives it (host only, never a kernel parameter).  The public and the fused
 // contract share the kernels' argument slots: loc / aw hold sampling locations and attention weights, or (fused) the raw
@@ -158,18 +171,5 @@ __device__ __forceinline__ void msda_job_sample(const float4 &la, const float4 &
     far = tl * (float)MSDA_PROBE_NEAR_DIV < tc;
 }
 int msda_launch_locality_probe(hipStream_t st, const float *loc, const int64_t *shapes, int B, int S, int M, int L, int *hits);
-
-template <typename T>
-inline MsdaFwdImpl msda_fwd_choose_impl(const T *value, const T *loc, const T *aw, const T *out, int B,
-                                        int S, int M, int D, int L, int Lq, int P)
-{
-    if (sizeof(T) != 4) return MsdaFwdImpl::Gather;
-    const int env = msda_fwd_impl_knob();
-    if (env == 1) return MsdaFwdImpl::Gather;
-    const bool a16 = ((reinterpret_cast<uintptr_t>(value) | reinterpret_cast<uintptr_t>(loc) |
-                       reinterpret_cast<uintptr_t>(aw) | reinterpret_cast<uintptr_t>(out)) % 16) == 0;
-    if (!msda_tile_supported(B, S, M, D, L, Lq, P, a16, 0, L)) return MsdaFwdImpl::Gather;
-    return MsdaFwdImpl::Tile;
-}
 
 }  // namespace mvdetr

@@ -20,26 +20,35 @@
 
 namespace mvdetr {
 
-static int impl_from_env()
-{
-    const char *e = getenv("MVDETR_MSDA_FWD_IMPL");
-    if (e && !strcmp(e, "gather")) return 1;
-    if (e && !strcmp(e, "tile")) return 2;
-    return 0;
-}
-
 static std::atomic<int> g_impl_knob{-1};
 
-int msda_fwd_impl_knob()
+// MVDETR_MSDA_FWD_IMPL = auto (default) | gather | tile; overridable at run time through mvdetr_msda_set_forward_impl()
+static MsdaFwdKnob msda_fwd_impl_knob()
 {
     int v = g_impl_knob.load(std::memory_order_relaxed);
     if (v < 0) {
-        v = impl_from_env();
+        v = (int)msda_forward_parse_knob(getenv("MVDETR_MSDA_FWD_IMPL"));
         int expect = -1;
         g_impl_knob.compare_exchange_strong(expect, v);
         v = g_impl_knob.load(std::memory_order_relaxed);
     }
-    return v;
+    return (MsdaFwdKnob)v;
+}
+
+// The environment's part of a route and of a camera-grouped launch's options, read once per process.  MVDETR_MSDA_GROUP=0
+// keeps every call off the camera-grouped kernels.
+static bool group_enabled()
+{
+    static const bool enabled = [] { const char *e = getenv("MVDETR_MSDA_GROUP"); return !(e && e[0] == '0'); }();
+    return enabled;
+}
+// MVDETR_MSDA_WINDOW_SHIFT=0 keeps the fused kernels' windows centred on the tile (A/B knob); the jobs are dealt to the XCDs as
+// 2-D blocks of the tile grid (GROUP_OPT_BLOCKS: 566 -> 314 MB of memory-side traffic per launch against bands of the job
+// list, round 4)
+static int group_opts(const MsdaFwdRoute &r)
+{
+    static const bool no_shift = [] { const char *e = getenv("MVDETR_MSDA_WINDOW_SHIFT"); return e && e[0] == '0'; }();
+    return ((r.ref_mode && no_shift) ? GROUP_OPT_NO_SHIFT : 0) | GROUP_OPT_BLOCKS | (r.standdown ? GROUP_OPT_STANDDOWN : 0);
 }
 
 template <typename T, int VEC>
@@ -78,25 +87,6 @@ static int launch_gather(hipStream_t st, const T *value, const int64_t *shapes, 
     return (int)hipGetLastError();
 }
 
-template <typename T>
-int msda_forward_gather(hipStream_t st, const T *value, const int64_t *shapes, const int64_t *lsi,
-                        const T *loc, const T *aw, int B, int S, int M, int D, int L, int Lq, int P,
-                        T *out)
-{
-    constexpr int WIDE = 16 / (int)sizeof(T);            // 4 floats / 2 doubles per 16-byte access
-    const bool a16 = aligned(value, 16) && aligned(out, 16);
-    if (a16 && D % WIDE == 0)
-        return launch_gather<T, WIDE>(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out);
-    return launch_gather<T, 1>(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out);
-}
-
-template int msda_forward_gather<float>(hipStream_t, const float *, const int64_t *, const int64_t *,
-                                        const float *, const float *, int, int, int, int, int, int, int,
-                                        float *);
-template int msda_forward_gather<double>(hipStream_t, const double *, const int64_t *, const int64_t *,
-                                         const double *, const double *, int, int, int, int, int, int,
-                                         int, double *);
-
 static thread_local const char *g_last_impl = "none";
 static thread_local const char *g_last_kernel = "none";
 static thread_local KernelResources g_last_resources = {-1, -1, -1};
@@ -106,9 +96,25 @@ void msda_note_forward_kernel(const char *name, const KernelResources *res)
     g_last_resources = res ? *res : KernelResources{-1, -1, -1};
 }
 
-static bool bad_dims(int B, int S, int M, int D, int L, int Lq, int P)
+// what mvdetr_msda_last_forward_impl() says of a route
+static const char *impl_name(MsdaFwdKind k)
 {
-    return B < 0 || S < 0 || M <= 0 || D <= 0 || L <= 0 || Lq < 0 || P <= 0;
+    if (k == MsdaFwdKind::gather) return "gather";
+    return k == MsdaFwdKind::tile || k == MsdaFwdKind::group2 || k == MsdaFwdKind::group_many ? "tile" : "tile_fused";
+}
+
+// the kernel of an fp32 route other than `gather`, and the statistics pass where the route has one
+static int launch_route(const MsdaFwdRoute &r, const MsdaFwdCall &c)
+{
+    int rc;
+    switch (r.kind) {
+    case MsdaFwdKind::tile: case MsdaFwdKind::fused_tile: rc = msda_forward_tile(c); break;
+    case MsdaFwdKind::group2: case MsdaFwdKind::fused_group2: rc = msda_forward_group2(c); break;
+    case MsdaFwdKind::group_many: case MsdaFwdKind::fused_group_many: rc = msda_forward_group_many(c); break;
+    default: return (int)hipErrorInvalidValue;
+    }
+    if (!rc && r.stats_pass) rc = msda_softmax_stats(c.st, c.aw, c.lay, (int64_t)c.B * c.qr.Lq, c.M, c.L, c.stats);
+    return rc;
 }
 
 template <typename T>
@@ -116,34 +122,55 @@ static int forward_entry(void *stream, const T *value, const int64_t *shapes, co
                          const T *loc, const T *aw, int B, int S, int M, int D, int L, int Lq, int P,
                          T *out)
 {
-    if (bad_dims(B, S, M, D, L, Lq, P)) return (int)hipErrorInvalidValue;
-    if ((int64_t)B * Lq == 0) { g_last_impl = "empty"; return 0; }     // nothing to write
+    const bool a16 = aligned(value, 16) && aligned(out, 16);
+    const MsdaFwdRoute r = msda_forward_route(MsdaFwdQuery{sizeof(T) == 4 ? MsdaFwdEntry::public_f32 : MsdaFwdEntry::public_f64, B, S, M, D, L, Lq, P,
+                                                           /*layout, strides*/ 0, 0, 0, /*query levels*/ 0, L, false,
+                                                           a16 && aligned(loc, 16) && aligned(aw, 16), a16, msda_fwd_impl_knob(),
+                                                           group_enabled(), false});
+    if (r.status == MsdaFwdStatus::invalid_value) return (int)hipErrorInvalidValue;
+    if (r.status == MsdaFwdStatus::empty) { g_last_impl = "empty"; return 0; }     // nothing to write
     if (!value || !shapes || !lsi || !loc || !aw || !out) return (int)hipErrorInvalidValue;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const MsdaFwdImpl impl = msda_fwd_choose_impl<T>(value, loc, aw, out, B, S, M, D, L, Lq, P);
-    if (impl == MsdaFwdImpl::Tile) {
-        g_last_impl = "tile";
-        if constexpr (sizeof(T) == 4) {
-            // `auto`: a device-side probe (stream-ordered scratch int, no host sync) tells the tile kernel whether the
-            // sampling locations are near the queries' cells; if not, the same launch runs the gather formulation.
-            // A forced `tile` skips the probe (the kernel is then measured as it is).
-            // (6 / 7 equal levels: msda_fwd_group2 looks at every tile's own taps and stands down job by job -- no probe
-            // kernel, no scratch allocation in front of the forward)
-            int *hits = nullptr;
-            if (msda_fwd_impl_knob() == 0 && msda_forward_tile_wants_probe(B, S, M, D, L) &&
-                hipMallocAsync(reinterpret_cast<void **>(&hits), MSDA_PROBE_INTS * sizeof(int), st) != hipSuccess)
-                hits = nullptr;
-            int rc = hits ? msda_launch_locality_probe(st, loc, shapes, B, S, M, L, hits) : 0;
-            if (!rc) rc = msda_forward_tile(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out, hits);
-            if (hits) (void)hipFreeAsync(hits, st);
-            return rc;
-        } else {
-            return msda_forward_tile(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out, nullptr);
-        }
+    g_last_impl = impl_name(r.kind);
+    if (r.kind == MsdaFwdKind::gather) {
+        msda_note_forward_kernel("msda_fwd_gather");
+        constexpr int WIDE = 16 / (int)sizeof(T);            // 4 floats / 2 doubles per 16-byte access
+        return r.gather_vec == 1 ? launch_gather<T, 1>(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out)
+                                 : launch_gather<T, WIDE>(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out);
     }
-    g_last_impl = "gather";
-    msda_note_forward_kernel("msda_fwd_gather");
-    return msda_forward_gather<T>(st, value, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, out);
+    if constexpr (sizeof(T) == 4) {
+        MsdaFwdCall c{st, value, shapes, lsi, loc, aw, /*ref*/ nullptr, 0, plain_layout(r.q_l, L * P * 2, P * 2, r.q_w, L * P, P),     // [.., Lq, M, L, P(, 2)]
+                      QueryLevels{0, L, S}, r.ref_mode, B, S, M, D, L, out, /*stats*/ nullptr, /*probe*/ nullptr, group_opts(r)};
+        // (if the probe's scratch cannot be had, the forward goes on without a probe)
+        int *hits = nullptr;
+        if (r.probe && hipMallocAsync(reinterpret_cast<void **>(&hits), MSDA_PROBE_INTS * sizeof(int), st) != hipSuccess) hits = nullptr;
+        int rc = hits ? msda_launch_locality_probe(st, loc, shapes, B, S, M, L, hits) : 0;
+        c.probe = hits;
+        if (!rc) rc = launch_route(r, c);
+        if (hits) (void)hipFreeAsync(hits, st);
+        return rc;
+    }
+    return (int)hipErrorInvalidValue;       // (fp64 has no route but `gather`)
+}
+
+// both fused entries.  stats: the training entry's softmax statistics, null for inference
+static int fused_entry(MsdaFwdEntry entry, void *stream, const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                       int64_t ref_bstride, const float *offsets, const float *logits, int layout, int qstride_l, int qstride_w,
+                       int ql0, int ql1, int B, int S, int M, int D, int L, int Lq, int P, float *out, float *stats)
+{
+    const bool a16 = aligned(value, 16) && aligned(out, 16);
+    const bool all16 = a16 && aligned(ref, 16) && aligned(offsets, 16) && aligned(logits, 16) && ref_bstride % ((layout & 2) ? 2 : 4) == 0;
+    // slice-interleaved layouts: the two pointers address one tensor, the logits start behind the first slice's offsets
+    const bool follow = reinterpret_cast<uintptr_t>(logits) == reinterpret_cast<uintptr_t>(offsets) + (uintptr_t)((int64_t)(D == 16 ? 2 : 1) * P * 2 * 4);
+    const MsdaFwdRoute r = msda_forward_route(MsdaFwdQuery{entry, B, S, M, D, L, Lq, P, layout, qstride_l, qstride_w, ql0, ql1, follow, all16, a16,
+                                                           msda_fwd_impl_knob(), group_enabled(), stats != nullptr});
+    if (r.status == MsdaFwdStatus::invalid_value) return (int)hipErrorInvalidValue;
+    if (!value || !shapes || !lsi || !ref || !offsets || !logits || !out) return (int)hipErrorInvalidValue;
+    if (r.status != MsdaFwdStatus::ok) return (int)hipErrorNotSupported;
+    g_last_impl = impl_name(r.kind);
+    return launch_route(r, MsdaFwdCall{reinterpret_cast<hipStream_t>(stream), value, shapes, lsi, offsets, logits, ref, ref_bstride,
+                                       fused_layout(layout, r.q_l, r.q_w, M, D, L, Lq), QueryLevels{ql0, ql1, Lq}, r.ref_mode, B, S, M, D, L,
+                                       out, stats, /*probe*/ nullptr, group_opts(r)});
 }
 
 }  // namespace mvdetr
@@ -166,7 +193,7 @@ const char *mvdetr_msda_last_forward_kernel(void) { return mvdetr::g_last_kernel
 int mvdetr_msda_set_forward_impl(int impl)
 {
     if (impl < 0 || impl > 2) impl = 0;
-    const int prev = mvdetr::msda_fwd_impl_knob();
+    const int prev = (int)mvdetr::msda_fwd_impl_knob();
     mvdetr::g_impl_knob.store(impl);
     return prev;
 }
@@ -199,54 +226,6 @@ int mvdetr_msda_forward_fused_f32(void *stream, const float *value, const int64_
                                                 out);
 }
 
-static int fused_entry(void *stream, const float *value, const int64_t *spatial_shapes,
-                       const int64_t *level_start_index, const float *reference_points,
-                       int64_t ref_batch_stride, const float *sampling_offsets,
-                       const float *attn_logits, int level_major, int offsets_query_stride,
-                       int logits_query_stride, int query_level_begin, int query_level_end,
-                       int batch, int spatial_size, int num_heads, int channels, int num_levels,
-                       int num_query, int num_point, float *out, float *stats)
-{
-    using namespace mvdetr;
-    const int dense_l = num_heads * num_levels * num_point * 2, dense_w = num_heads * num_levels * num_point;
-    if (offsets_query_stride == 0) offsets_query_stride = dense_l;
-    if (logits_query_stride == 0) logits_query_stride = dense_w;
-    if (offsets_query_stride < dense_l || logits_query_stride < dense_w || offsets_query_stride % 4 || logits_query_stride % 4)
-        return (int)hipErrorInvalidValue;
-    if (bad_dims(batch, spatial_size, num_heads, channels, num_levels, num_query, num_point))
-        return (int)hipErrorInvalidValue;
-    if (query_level_begin < 0 || query_level_end <= query_level_begin || query_level_end > num_levels)
-        return (int)hipErrorInvalidValue;
-    // bit 0 level-major raw tensors, bit 1 one reference point per (query, level), bit 2 slice-interleaved raw tensor
-    // (offsets and logits in one run per (query, slice, level); excludes bit 0), bit 3 level-major reference points
-    // [.., L, Lq, 2] (needs bit 1), bit 4 the slice-interleaved tensor with the LEVEL outermost, [.., Lq, L, M/g, run]
-    // (needs bit 2)
-    if ((level_major & ~31) || ((level_major & 4) && (level_major & 1)) || ((level_major & 8) && !(level_major & 2)) ||
-        ((level_major & 16) && !(level_major & 4)))
-        return (int)hipErrorInvalidValue;
-    if (level_major & 4) {
-        // the two pointers address one tensor: logits start behind the slice's offsets
-        const int hps = channels == 16 ? 2 : 1;
-        if ((channels != 16 && channels != 32) || attn_logits != sampling_offsets + hps * num_point * 2 ||
-            offsets_query_stride != logits_query_stride || offsets_query_stride < dense_l + dense_w)
-            return (int)hipErrorInvalidValue;
-    }
-    if (!value || !spatial_shapes || !level_start_index || !reference_points || !sampling_offsets || !attn_logits || !out)
-        return (int)hipErrorInvalidValue;
-    const bool a16 = ((reinterpret_cast<uintptr_t>(value) | reinterpret_cast<uintptr_t>(reference_points) |
-                       reinterpret_cast<uintptr_t>(sampling_offsets) | reinterpret_cast<uintptr_t>(attn_logits) |
-                       reinterpret_cast<uintptr_t>(out)) % 16) == 0 && ref_batch_stride % ((level_major & 2) ? 2 : 4) == 0;
-    if (!msda_tile_supported(batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, a16,
-                             query_level_begin, query_level_end))
-        return (int)hipErrorNotSupported;
-    g_last_impl = "tile_fused";
-    return msda_forward_tile_fused(reinterpret_cast<hipStream_t>(stream), value, spatial_shapes, level_start_index,
-                                   reference_points, ref_batch_stride, sampling_offsets, attn_logits,
-                                   level_major, offsets_query_stride, logits_query_stride, query_level_begin,
-                                   query_level_end, num_query, batch, spatial_size, num_heads, channels, num_levels,
-                                   out, stats);
-}
-
 int mvdetr_msda_forward_fused_levels_f32(void *stream, const float *value, const int64_t *spatial_shapes,
                                          const int64_t *level_start_index, const float *reference_points,
                                          int64_t ref_batch_stride, const float *sampling_offsets,
@@ -255,9 +234,9 @@ int mvdetr_msda_forward_fused_levels_f32(void *stream, const float *value, const
                                          int batch, int spatial_size, int num_heads, int channels, int num_levels,
                                          int num_query, int num_point, float *out)
 {
-    return fused_entry(stream, value, spatial_shapes, level_start_index, reference_points, ref_batch_stride, sampling_offsets,
-                       attn_logits, level_major, offsets_query_stride, logits_query_stride, query_level_begin, query_level_end,
-                       batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, out, nullptr);
+    return mvdetr::fused_entry(mvdetr::MsdaFwdEntry::fused, stream, value, spatial_shapes, level_start_index, reference_points, ref_batch_stride,
+                               sampling_offsets, attn_logits, level_major, offsets_query_stride, logits_query_stride, query_level_begin,
+                               query_level_end, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, out, nullptr);
 }
 
 int mvdetr_msda_fused_train_supported(int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
@@ -276,14 +255,15 @@ int mvdetr_msda_forward_fused_train_f32(void *stream, const float *value, const 
                                         float *out, float *stats)
 {
     if (!stats || !raw) return (int)hipErrorInvalidValue;
+    // (refused here as well as by the route: this refusal precedes the entry's look at the other pointers)
     if (!mvdetr_msda_fused_train_supported(batch, spatial_size, num_heads, channels, num_levels, spatial_size, num_point))
         return (int)hipErrorNotSupported;
     const int hps = channels == 16 ? 2 : 1;
     // layout: the slice-interleaved raw tensor with the level outermost (bits 2 and 4), one reference point per
     // (query, level), level-major (bits 1 and 3)
-    return fused_entry(stream, value, spatial_shapes, level_start_index, reference_points, ref_batch_stride, raw,
-                       raw + hps * num_point * 2, 2 | 4 | 8 | 16, raw_query_stride, raw_query_stride, 0, num_levels, batch,
-                       spatial_size, num_heads, channels, num_levels, spatial_size, num_point, out, stats);
+    return mvdetr::fused_entry(mvdetr::MsdaFwdEntry::fused_train, stream, value, spatial_shapes, level_start_index, reference_points,
+                               ref_batch_stride, raw, raw + hps * num_point * 2, 2 | 4 | 8 | 16, raw_query_stride, raw_query_stride, 0,
+                               num_levels, batch, spatial_size, num_heads, channels, num_levels, spatial_size, num_point, out, stats);
 }
 
 int mvdetr_msda_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,

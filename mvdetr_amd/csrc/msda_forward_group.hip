@@ -21,21 +21,6 @@
 
 namespace mvdetr {
 
-bool msda_group_supported(int D, int L)
-{
-    static const bool enabled = [] { const char *e = getenv("MVDETR_MSDA_GROUP"); return !(e && e[0] == '0'); }();
-    return enabled && (D == 16 || D == 32) && (L == 6 || L == 7 || (L >= 9 && L <= 16));
-}
-
-// options of a launch, from the environment (read once): MVDETR_MSDA_WINDOW_SHIFT=0 keeps the fused kernels' windows centred
-// on the tile (A/B knob); the jobs are dealt to the XCDs as 2-D blocks of the tile grid (GROUP_OPT_BLOCKS: 566 -> 314 MB of
-// memory-side traffic per launch against bands of the job list, round 4)
-static int group_opts(int fused)
-{
-    static const bool no_shift = [] { const char *e = getenv("MVDETR_MSDA_WINDOW_SHIFT"); return e && e[0] == '0'; }();
-    return ((fused && no_shift) ? GROUP_OPT_NO_SHIFT : 0) | GROUP_OPT_BLOCKS;
-}
-
 #ifdef MVDETR_GROUP_TRACE
 __device__ unsigned long long *g_group_trace = nullptr;
 #endif
@@ -44,26 +29,21 @@ __device__ unsigned long long *g_group_trace = nullptr;
 // slower -- registers)
 constexpr int GROUP2_DEPTH = 2;
 
-int msda_forward_group(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *off, const float *logit, const float *ref, int64_t ref_bstride, int fused,
-                       SamplingLayout lay, int B, int S, int M, int D, int L, float *out, const int *local_hits, bool standdown,
-                       float *stats)
+// 6 / 7 cameras: the software-pipelined kernel (msda_group2_kernel.h) for every entry -- fused (raw offsets / logits, one
+// or P reference points per (query, level)) and the public contract (final locations / weights)
+template <typename Cfg, int L>
+static int group2_of_ref_mode(const MsdaFwdCall &c)
 {
-    const int opts = group_opts(fused) | ((standdown && !fused) ? GROUP_OPT_STANDDOWN : 0);
-#define GROUP_ARGS st, value, shapes, lsi, off, logit, ref, ref_bstride, lay, B, S, M, out, local_hits, opts
-    if (L >= 9 && L <= 16) {           // many cameras: 4 lane groups x up to 4 cameras (msda_forward_group_many.hip)
-        return msda_forward_group_many(st, value, shapes, lsi, off, logit, ref, ref_bstride, fused, lay, B, S, M, D, L, out,
-                                       local_hits, opts, fused ? stats : nullptr);
-    }
-    // 6 / 7 cameras: the software-pipelined kernel (msda_group2_kernel.h) for every entry -- fused (raw offsets / logits, one
-    // or P reference points per (query, level)) and the public contract (final locations / weights)
-#define G2(CFG, LL) (fused == 2 ? launch_group2<CFG, LL, 2, GROUP2_DEPTH>(GROUP_ARGS, stats) : fused ? launch_group2<CFG, LL, 1, GROUP2_DEPTH>(GROUP_ARGS, stats) \
-                                                                                                  : launch_group2<CFG, LL, 0, GROUP2_DEPTH>(GROUP_ARGS))
-    if (D == 16 && L == 7) return G2(GWide16, 7);
-    if (D == 16 && L == 6) return G2(GWide16, 6);
-    if (D == 32 && L == 7) return G2(GWide32, 7);
-    if (D == 32 && L == 6) return G2(GWide32, 6);
-#undef G2
+    return c.ref_mode == 2 ? launch_group2<Cfg, L, 2, GROUP2_DEPTH>(c) : c.ref_mode ? launch_group2<Cfg, L, 1, GROUP2_DEPTH>(c)
+                                                                                    : launch_group2<Cfg, L, 0, GROUP2_DEPTH>(c);
+}
+
+int msda_forward_group2(const MsdaFwdCall &c)
+{
+    if (c.D == 16 && c.L == 7) return group2_of_ref_mode<GWide16, 7>(c);
+    if (c.D == 16 && c.L == 6) return group2_of_ref_mode<GWide16, 6>(c);
+    if (c.D == 32 && c.L == 7) return group2_of_ref_mode<GWide32, 7>(c);
+    if (c.D == 32 && c.L == 6) return group2_of_ref_mode<GWide32, 6>(c);
     return (int)hipErrorInvalidValue;
 }
 

@@ -10,12 +10,10 @@
 // one contiguous 64-byte token segment per bilinear corner.
 #include "common.h"
 #include "half_types.h"
+#include "msda_dispatch.h"
 #include "../../include/mvdetr_ops.h"
 
 namespace mvdetr {
-
-struct KernelResources;
-void msda_note_forward_kernel(const char *name, const KernelResources *res = nullptr);
 
 template <typename C, int VEC>
 __global__ __launch_bounds__(256) void msda_fwd_gather_half(

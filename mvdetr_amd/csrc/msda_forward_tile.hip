@@ -83,103 +83,29 @@ int msda_softmax_stats(hipStream_t st, const float *logits, SamplingLayout lay, 
 }
 
 template <typename Cfg, int FUSED>
-static int launch_tile(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *aw, const float *ref, int64_t ref_bstride, SamplingLayout lay,
-                       QueryLevels qr, int B, int S, int M, int L, float *out, const int *local_hits)
+static int launch_tile(const MsdaFwdCall &c)
 {
     static PersistentGrid grid;
     const int blocks = grid.occupancy(&msda_fwd_tile<Cfg, FUSED>, Cfg::THREADS, Cfg::LDS_BYTES, 2);
     static const KernelResources res = kernel_resources(reinterpret_cast<const void *>(&msda_fwd_tile<Cfg, FUSED>));
     msda_note_forward_kernel("msda_fwd_tile", &res);
-    hipLaunchKernelGGL((msda_fwd_tile<Cfg, FUSED>), dim3((unsigned)blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES,
-                       st, value, shapes, lsi, loc, aw, ref, ref_bstride, lay, qr, B, S, M, L, out, local_hits);
+    hipLaunchKernelGGL((msda_fwd_tile<Cfg, FUSED>), dim3((unsigned)blocks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, c.st, c.value, c.shapes, c.lsi,
+                       c.loc, c.aw, c.ref, c.ref_bstride, c.lay, c.qr, c.B, c.S, c.M, c.L, c.out, c.probe);
     return (int)hipGetLastError();
 }
 
-#define TILE_ARGS st, value, shapes, lsi, loc, aw, ref, ref_bstride, lay, qr, B, S, M, L, out, local_hits
+template <typename Cfg>
+static int tile_of_ref_mode(const MsdaFwdCall &c)
+{
+    return c.ref_mode == 2 ? launch_tile<Cfg, 2>(c) : c.ref_mode ? launch_tile<Cfg, 1>(c) : launch_tile<Cfg, 0>(c);
+}
 
-template <int FUSED>
-static int dispatch_tile(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                         const float *loc, const float *aw, const float *ref, int64_t ref_bstride, SamplingLayout lay,
-                         QueryLevels qr, int B, int S, int M, int D, int L, float *out, const int *local_hits = nullptr)
+int msda_forward_tile(const MsdaFwdCall &c)
 {
     // (128-byte slices; 64-byte ones -- twice the workgroups per CU -- were measured slower: DESIGN 5.2)
-    if (D == 16) return launch_tile<CfgWide16, FUSED>(TILE_ARGS);
-    if (D == 32) return launch_tile<CfgWide32, FUSED>(TILE_ARGS);
+    if (c.D == 16) return tile_of_ref_mode<CfgWide16>(c);
+    if (c.D == 32) return tile_of_ref_mode<CfgWide32>(c);
     return (int)hipErrorInvalidValue;
-}
-
-static bool group2_takes(int B, int S, int M, int D, int L, const SamplingLayout &lay)
-{
-    return msda_group_supported(D, L) && L <= 7 && msda_group_fits(B, S, M * D, lay);
-}
-
-bool msda_forward_tile_wants_probe(int B, int S, int M, int D, int L)
-{
-    return !group2_takes(B, S, M, D, L, plain_layout(M * L * TILE_P * 2, L * TILE_P * 2, TILE_P * 2, M * L * TILE_P, L * TILE_P, TILE_P));
-}
-
-int msda_forward_tile(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                      const float *loc, const float *aw, int B, int S, int M, int D, int L, int Lq,
-                      int P, float *out, const int *local_hits)
-{
-    const SamplingLayout lay = plain_layout(M * L * P * 2, L * P * 2, P * 2, M * L * P, L * P, P);     // [.., Lq, M, L, P(, 2)]
-    // camera-grouped kernel also for the public (unfused) contract: 188 vs 197 us at Wildtrack size -- the
-    // reference layout re-touches every sampling_loc line in 4 level iterations, so the gain is small
-    if (msda_group_supported(D, L) && msda_group_fits(B, S, M * D, lay))
-        return msda_forward_group(st, value, shapes, lsi, loc, aw, nullptr, 0, 0, lay, B, S, M, D, L, out, local_hits,
-                                  /*standdown=*/msda_fwd_impl_knob() == 0);
-    return dispatch_tile<0>(st, value, shapes, lsi, loc, aw, nullptr, 0, lay, QueryLevels{0, L, S}, B, S, M, D, L, out, local_hits);
-}
-
-int msda_forward_tile_fused(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                            const float *ref, int64_t ref_bstride, const float *offsets, const float *logits,
-                            int layout, int qstride_l, int qstride_w, int ql0, int ql1, int Lq, int B, int S,
-                            int M, int D, int L, float *out, float *stats)
-{
-    const int level_major = layout & 1, shared_ref = layout & 2, slice_major = layout & 4, ref_level_major = layout & 8;
-    const int P = TILE_P;
-    // reference points: [.., Lq, L, P, 2], [.., Lq, L, 2] (shared_ref) or [.., L, Lq, 2] (shared_ref + ref_level_major)
-    const int r_q = ref_level_major ? 2 : L * (shared_ref ? 2 : P * 2);
-    const int r_l = ref_level_major ? Lq * 2 : (shared_ref ? 2 : P * 2);
-    SamplingLayout lay;
-    if (slice_major) {
-        // one tensor [.., Lq, M / hps, L, (hps x P x 2 offsets | hps x P logits)]: what the workgroup of a 128-byte
-        // slice reads for a (query, level) is one contiguous run of hps * 12 floats; `logits` = `offsets` + hps * 8
-        // Bit 4: the level is the OUTER index, [.., Lq, L, M / hps, run] -- a (query, level)'s runs of all slices are then
-        // M / hps * chunk * 4 = 384 contiguous bytes = three whole 128-byte lines (at D = 16, M = 8), shared by the four
-        // slice jobs of a tile, which run at the same time on one XCD (one L2); with the slice outermost a run shares its
-        // lines with the same slice's NEXT level, i.e. with a later phase of the same job, by when the line has left L2.
-        const int hps = 32 / D, chunk = hps * P * 3;
-        if (layout & 16)
-            lay = SamplingLayout{qstride_l, P * 2, (M / hps) * chunk, qstride_w, P, (M / hps) * chunk, hps, chunk, chunk, r_q, r_l};
-        else
-            lay = SamplingLayout{qstride_l, P * 2, chunk, qstride_w, P, chunk, hps, L * chunk, L * chunk, r_q, r_l};
-    } else if (level_major) {
-        lay = plain_layout(qstride_l, P * 2, M * P * 2, qstride_w, P, M * P, r_q, r_l);              // [.., Lq, L, M, P(, 2)]
-    } else {
-        lay = plain_layout(qstride_l, L * P * 2, P * 2, qstride_w, L * P, P, r_q, r_l);              // [.., Lq, M, L, P(, 2)]
-    }
-    // MVDeTr's camera counts: the camera-grouped kernel (which falls back to this file's tile body, in the
-    // same launch, when the levels turn out on the device to have unequal shapes) -- msda_forward_group.hip
-    // A query-sharded call (a rank's own cameras as queries, mvdetr_amd/dist.py) has too few query levels per
-    // window to amortise the grouped staging and runs the tile kernel.
-    const bool all_levels = ql0 == 0 && ql1 == L;
-    const bool grouped = all_levels && msda_group_supported(D, L) && msda_group_fits(B, S, M * D, lay);
-    // the training entry's statistics: the camera-grouped kernels (6 / 7 levels: msda_fwd_group2; 9 - 16: msda_fwd_group) write them
-    // themselves; the tile kernel runs as it does for inference and a small pass over the logits follows
-    const bool own_stats = grouped;
-    int rc;
-    if (grouped)
-        rc = msda_forward_group(st, value, shapes, lsi, offsets, logits, ref, ref_bstride, shared_ref ? 2 : 1, lay, B, S,
-                                M, D, L, out, nullptr, false, own_stats ? stats : nullptr);
-    else
-        rc = shared_ref ? dispatch_tile<2>(st, value, shapes, lsi, offsets, logits, ref, ref_bstride, lay,
-                                           QueryLevels{ql0, ql1, Lq}, B, S, M, D, L, out)
-                        : dispatch_tile<1>(st, value, shapes, lsi, offsets, logits, ref, ref_bstride, lay,
-                                           QueryLevels{ql0, ql1, Lq}, B, S, M, D, L, out);
-    if (!rc && stats && !own_stats) rc = msda_softmax_stats(st, logits, lay, (int64_t)B * Lq, M, L, stats);
-    return rc;
 }
 
 }  // namespace mvdetr

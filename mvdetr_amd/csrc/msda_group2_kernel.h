@@ -602,10 +602,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void msda_fwd_group2(
 }
 
 template <typename Cfg, int NG, int FUSED, int DEPTH>
-static int launch_group2(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                         const float *off, const float *logit, const float *ref, int64_t ref_bstride,
-                         SamplingLayout lay, int B, int S, int M, float *out, const int *local_hits, int opts,
-                         float *stats = nullptr)
+static int launch_group2(const MsdaFwdCall &c)
 {
     constexpr int FB = TileCfg<Cfg::D, 32, 8, 16, 6>::LDS_BYTES;
     constexpr int LDS = Group2Lds<Cfg, NG>::BYTES > FB ? Group2Lds<Cfg, NG>::BYTES : FB;
@@ -614,7 +611,8 @@ static int launch_group2(hipStream_t st, const float *value, const int64_t *shap
     const int blocks = grid.occupancy(kernel, Cfg::THREADS, LDS, 2);
     static const KernelResources res = kernel_resources(reinterpret_cast<const void *>(&msda_fwd_group2<Cfg, NG, FUSED, DEPTH>));
     msda_note_forward_kernel("msda_fwd_group2[pipelined taps, LDS-DMA windows]", &res);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, st, value, shapes, lsi, off, logit, ref, ref_bstride, lay, B, S, M, out, local_hits, opts, stats);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, c.st, c.value, c.shapes, c.lsi, c.loc, c.aw, c.ref, c.ref_bstride, c.lay,
+                       c.B, c.S, c.M, c.out, c.probe, c.opts, c.stats);
     return (int)hipGetLastError();
 }
 

@@ -14,10 +14,7 @@
 #define MVDETR_SHIFT_MAX 3
 #endif
 
-// kernel options (the `opts` argument)
-#define GROUP_OPT_NO_SHIFT 1      // keep the windows centred on the tile (A/B knob MVDETR_MSDA_WINDOW_SHIFT=0)
-#define GROUP_OPT_BLOCKS 2        // XCD k takes a 2-D block of the tile grid instead of a band of the job list
-#define GROUP_OPT_STANDDOWN 4     // (msda_fwd_group2, public contract) a job whose taps are far from its cells gathers instead
+// (kernel options, the `opts` argument: GROUP_OPT_* of msda_dispatch.h)
 // -DMVDETR_GROUP_TRACE builds (libmvdetr_ops_trace.so, tools/experiments/group_trace.py): every wave's lane 0 stamps the
 // 100 MHz wall clock at the phase boundaries of its workgroup's FIRST job into a global table
 // [workgroup][wave 0..3][GROUP_TRACE_SLOTS]: 0 kernel entry, 1 shift known, 2 + 2l level l's window resident, 3 + 2l its
@@ -492,9 +489,7 @@ using GQuad16 = TileCfg<16, 32, MVDETR_QUAD_TH, 16, 6, MVDETR_QUAD_TH * 16 * 2 *
 using GQuad32 = TileCfg<32, 32, MVDETR_QUAD_TH, 16, 6, MVDETR_QUAD_TH * 16 * 2 * 4>;
 
 template <typename Cfg, int NG, int WAVES, int FUSED, int SPLIT = 1, bool DMA = false>
-static int launch_group(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                        const float *off, const float *logit, const float *ref, int64_t ref_bstride,
-                        SamplingLayout lay, int B, int S, int M, float *out, const int *local_hits, int opts, float *stats = nullptr)
+static int launch_group(const MsdaFwdCall &c)
 {
     // dynamic LDS: the larger of this kernel's window and the fallback body's
     constexpr int LDS = Cfg::LDS_BYTES > TileCfg<Cfg::D, 32, 8, 16, 6>::LDS_BYTES ? Cfg::LDS_BYTES
@@ -505,7 +500,8 @@ static int launch_group(hipStream_t st, const float *value, const int64_t *shape
     static const KernelResources res = kernel_resources(reinterpret_cast<const void *>(&msda_fwd_group<Cfg, NG, WAVES, FUSED, SPLIT, DMA>));
     msda_note_forward_kernel(DMA ? (SPLIT > 1 ? "msda_fwd_group[camera-split, LDS-DMA windows]" : "msda_fwd_group[LDS-DMA windows]")
                                  : (SPLIT > 1 ? "msda_fwd_group[camera-split]" : "msda_fwd_group"), &res);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, st, value, shapes, lsi, off, logit, ref, ref_bstride, lay, B, S, M, out, local_hits, opts, stats);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Cfg::THREADS), LDS, c.st, c.value, c.shapes, c.lsi, c.loc, c.aw, c.ref, c.ref_bstride, c.lay,
+                       c.B, c.S, c.M, c.out, c.probe, c.opts, c.stats);
     return (int)hipGetLastError();
 }
 

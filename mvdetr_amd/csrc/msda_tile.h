@@ -2,7 +2,7 @@
 // msda_backward_*.hip).  Internal, not part of the C ABI.
 #pragma once
 #include "common.h"
-#include "msda_limits.h"
+#include "msda_forward_route.h"
 
 namespace mvdetr {
 
@@ -66,32 +66,27 @@ struct QueryLevels {
     int begin, end, Lq;
 };
 
-// the fused training forward's statistics -- (maximum, 1 / sum exp) of a (query, head)'s L x P logits -- for calls whose forward
-// kernel does not write them itself (msda_fwd_group2 does): msda_forward_tile.hip
-int msda_softmax_stats(hipStream_t st, const float *logits, SamplingLayout lay, int64_t queries, int M, int L, float *stats);
-
-// camera-grouped fused forward (msda_forward_group.hip)
-bool msda_group_supported(int D, int L);
-// its per-lane addresses are 32-bit float offsets from per-batch, per-camera bases: one batch element's reference points and
-// output must each stay below 2^32 bytes -- and the WHOLE sampling tensors (all B elements), because msda_fwd_group2 folds the
-// batch index into the 32-bit scalar offset of one whole-tensor buffer descriptor (per-batch descriptors cost the headline
-// instantiation its zero-scratch build: ADVICE r04).  Anything larger runs the tile kernel: 64-bit addresses.
-inline bool msda_group_fits(int B, int S, int row, const SamplingLayout &lay)
+// The fused entries' layout bits (msda_forward_route.h) as a SamplingLayout.  q_l, q_w: the query strides of offsets and logits.
+inline SamplingLayout fused_layout(int layout, int q_l, int q_w, int M, int D, int L, int Lq)
 {
-    const int64_t lim = (int64_t)1 << 30;                   // floats
-    return (int64_t)B * S * lay.q_l < lim && (int64_t)B * S * lay.q_w < lim && (int64_t)S * lay.r_q < lim && (int64_t)S * row < lim;
+    const int P = TILE_P;
+    // reference points: [.., Lq, L, P, 2], [.., Lq, L, 2] (shared_ref) or [.., L, Lq, 2] (shared_ref + ref_level_major)
+    const int r_q = msda_fused_ref_query_stride(layout, L);
+    const int r_l = (layout & 8) ? Lq * 2 : ((layout & 2) ? 2 : P * 2);
+    if (layout & 4) {
+        // one tensor [.., Lq, M / hps, L, (hps x P x 2 offsets | hps x P logits)]: what the workgroup of a 128-byte
+        // slice reads for a (query, level) is one contiguous run of hps * 12 floats; `logits` = `offsets` + hps * 8
+        // Bit 4: the level is the OUTER index, [.., Lq, L, M / hps, run] -- a (query, level)'s runs of all slices are then
+        // M / hps * chunk * 4 = 384 contiguous bytes = three whole 128-byte lines (at D = 16, M = 8), shared by the four
+        // slice jobs of a tile, which run at the same time on one XCD (one L2); with the slice outermost a run shares its
+        // lines with the same slice's NEXT level, i.e. with a later phase of the same job, by when the line has left L2.
+        const int hps = 32 / D, chunk = hps * P * 3;
+        if (layout & 16) return SamplingLayout{q_l, P * 2, (M / hps) * chunk, q_w, P, (M / hps) * chunk, hps, chunk, chunk, r_q, r_l};
+        return SamplingLayout{q_l, P * 2, chunk, q_w, P, chunk, hps, L * chunk, L * chunk, r_q, r_l};
+    }
+    if (layout & 1) return plain_layout(q_l, P * 2, M * P * 2, q_w, P, M * P, r_q, r_l);              // [.., Lq, L, M, P(, 2)]
+    return plain_layout(q_l, L * P * 2, P * 2, q_w, L * P, P, r_q, r_l);                              // [.., Lq, M, L, P(, 2)]
 }
-// fused: 0 = final locations / weights (ref unused), 1 = raw + reference points [.., Lq, L, P, 2], 2 = raw + one
-// reference point per (query, level) [.., Lq, L, 2]
-int msda_forward_group(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *off, const float *logit, const float *ref, int64_t ref_bstride, int fused,
-                       SamplingLayout lay, int B, int S, int M, int D, int L, float *out,
-                       const int *local_hits = nullptr, bool standdown = false, float *stats = nullptr);
-// its many-camera instantiations (msda_forward_group_many.hip); `opts`: GROUP_OPT_* of msda_group_kernel.h
-int msda_forward_group_many(hipStream_t st, const float *value, const int64_t *shapes, const int64_t *lsi,
-                            const float *off, const float *logit, const float *ref, int64_t ref_bstride, int fused,
-                            SamplingLayout lay, int B, int S, int M, int D, int L, float *out, const int *local_hits,
-                            int opts, float *stats = nullptr);
 
 // Tile count of one level, recomputed by every workgroup from the device-side shapes (uniform ->
 // scalar registers).

@@ -123,7 +123,7 @@ def _child(family, out_path):
         for case in FWD_CASES:
             value, shapes, lsi, loc, aw = [x.cuda() for x in _fwd_case(case)]
             out = MSDA.ms_deform_attn_forward(value, shapes, lsi, loc, aw, 64).cpu()
-            results[case] = [out, MSDA.last_forward_impl()]
+            results[case] = [out, MSDA.last_forward_impl(), MSDA.last_forward_kernel()]
     elif family == "warp":
         from mvdetr_amd.ops import warp_perspective
         from mvdetr_amd.ops import warp as warp_mod
@@ -231,6 +231,17 @@ def test_backward_routes_per_block_under_mass_skew(case, env):
     assert_skew_bars(case, _run_child("bwd", env)["skew:" + case])
 
 
+def _expected_fwd_kernel(case, env):
+    """The prefix of the kernel name mvdetr_msda_last_forward_kernel() must report (csrc/msda_forward_route.h; INTEGRATION.md,
+    knob table): 7 cameras run msda_fwd_group2 and 9 msda_fwd_group, by default and under a forced `tile`;
+    MVDETR_MSDA_GROUP=0 leaves msda_fwd_tile; `gather` msda_fwd_gather."""
+    if env.get("MVDETR_MSDA_FWD_IMPL") == "gather":
+        return "msda_fwd_gather"
+    if env.get("MVDETR_MSDA_GROUP") == "0":
+        return "msda_fwd_tile"
+    return "msda_fwd_group[" if case == "fwd_encoder_d32" else "msda_fwd_group2"
+
+
 @pytest.mark.parametrize("env", FWD_ROUTES, ids=_route_id)
 @pytest.mark.parametrize("case", FWD_CASES)
 def test_forward_routes_vs_oracle(case, env):
@@ -238,8 +249,9 @@ def test_forward_routes_vs_oracle(case, env):
     from oracle import c_oracle
     value, shapes, lsi, loc, aw = _fwd_case(case)
     want = c_oracle.msda_forward(value.double(), shapes, lsi, loc.double(), aw.double())
-    out, impl = _run_child("fwd", env)[case]
+    out, impl, kernel = _run_child("fwd", env)[case]
     assert (out.double() - want.view_as(out)).abs().max().item() < 1e-4
+    assert kernel.startswith(_expected_fwd_kernel(case, env)), (case, env, kernel)
     if env.get("MVDETR_MSDA_FWD_IMPL") == "gather":
         assert impl == "gather"
     if env.get("MVDETR_MSDA_FWD_IMPL") == "tile":

@@ -377,14 +377,14 @@ def test_auto_dispatch_rules(msda_impl):
     MSDA.set_forward_impl("auto")
     args = encoder_msda_inputs(7, 16, 24, seed=1)
     MSDA.ms_deform_attn_forward(*dev(*args), 64)
-    assert MSDA.last_forward_impl() == "tile"
+    assert MSDA.last_forward_impl() == "tile" and MSDA.last_forward_kernel().startswith("msda_fwd_group2")
     # decoder-style call (Lq != S), fp64, D = 30, P != 4: gather
     for a in (random_msda_inputs(1, [(8, 8)], 8, 16, 10, 4),
               [x.double() if x.is_floating_point() else x for x in args],
               random_msda_inputs(1, [(4, 4)], 2, 30, 16, 4),
               random_msda_inputs(1, [(4, 4)], 2, 16, 16, 3)):
         MSDA.ms_deform_attn_forward(*dev(*a), 64)
-        assert MSDA.last_forward_impl() == "gather"
+        assert MSDA.last_forward_impl() == "gather" and MSDA.last_forward_kernel().startswith("msda_fwd_gather")
 
 
 @pytest.mark.parametrize("L,D", [(7, 16), (6, 32)])
