@@ -210,6 +210,10 @@ int mvdetr_msda_backward_fused_f32(void *stream, const float *grad_output, const
  * (value 2): src is [n, src_h, src_w, channels] -- what a channels_last trunk produces -- so every bilinear
  * corner is one contiguous channel vector; supported together with bit 0 (value 3), channels a multiple of
  * 16 bytes, 16-byte aligned pointers; hipErrorNotSupported (801) otherwise.  Other bits: hipErrorInvalidValue.
+ * Which kernel every warp entry below runs, what it refuses with which code and what it accepts without a launch is ONE table,
+ * warp_route() of csrc/warp_route.h (plain C++; tests/test_warp_route.py prints it on the CPU, tests/test_warp_refusals_gpu.py
+ * checks the codes on the library).  The entries are in csrc/warp_perspective.hip, the kernels and their launchers in
+ * csrc/warp_forward.hip and csrc/warp_backward.hip.
  */
 int mvdetr_warp_perspective_forward_f32(void *stream, const float *src, const float *M, int n,
                                         int channels, int src_h, int src_w, int dst_h, int dst_w,

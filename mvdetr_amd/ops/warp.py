@@ -76,6 +76,17 @@ def release_scratch() -> None:
     _lib.check(_lib.lib().mvdetr_warp_release_scratch(), "mvdetr_warp_release_scratch")
 
 
+def _chunks_and_offsets(c, h, w, element_size):
+    """What the channel-last kernels ask of a view (csrc/warp_route.h): whole 16-byte chunks per pixel, and element offsets
+    inside the view that fit an int, h * w * C <= 2^31 - 1."""
+    return (c * element_size) % 16 == 0 and h * w * c <= 0x7fffffff
+
+
+def _plan_knobs():
+    """The library's knobs that change a plan's CONTENTS (csrc/warp_route.h, WarpKnobs.plan_key): part of the plan cache's key."""
+    return os.environ.get("MVDETR_WARP_BWD_GEOMETRY"), os.environ.get("MVDETR_WARP_BWD_HEAVY")
+
+
 def _channel_last_source(src, channels_last_out):
     """True when ``src`` ([N,C,h,w] shape) already lies in memory as [N,h,w,C] and a channel-last kernel takes it
     (NHWC destination: any float dtype; NCHW destination: float32 and the 16-bit types): then the warp reads it in place
@@ -83,11 +94,11 @@ def _channel_last_source(src, channels_last_out):
     n, c, h, w = src.shape
     return ((channels_last_out or src.dtype == torch.float32 or src.dtype in HALF_DTYPES) and src.is_cuda and c > 1 and h * w > 1
             and src.is_contiguous(memory_format=torch.channels_last)
-            and not src.is_contiguous() and (c * src.element_size()) % 16 == 0 and src.data_ptr() % 16 == 0)
+            and not src.is_contiguous() and _chunks_and_offsets(c, h, w, src.element_size()) and src.data_ptr() % 16 == 0)
 
 
 class _BackwardPlans:
-    """Plans of the gather backward (csrc/warp_perspective.hip: which destination pixels can touch each 2x2 block of source
+    """Plans of the gather backward (csrc/warp_backward.hip: which destination pixels can touch each 2x2 block of source
     texels) for the matrices seen lately.  A plan depends on M and the shapes only, so training without augmentation -- the
     same projection matrices every iteration -- builds it once and every backward is ONE kernel.  Entries hold the matrix
     tensor itself (its storage cannot be handed to another tensor while cached) and its version counter; writes through
@@ -110,7 +121,7 @@ class _BackwardPlans:
         n, c, h, w, H, W = shapes
         stream = _lib.current_stream_ptr(M.device)
         part_key = (M.device.index, int(stream or 0))
-        key = (shapes, os.environ.get("MVDETR_WARP_BWD_GEOMETRY"), os.environ.get("MVDETR_WARP_BWD_HEAVY"))
+        key = (shapes,) + _plan_knobs()
         with self.lock:
             entries = self.parts.pop(part_key, [])
             self.parts[part_key] = entries                  # (most recently used partition last)
@@ -162,7 +173,7 @@ class WarpPerspectiveFunction(Function):
         if not src_cl:
             src = src.contiguous()
             if (channels_last_out and src.is_cuda and c > 1 and h * w > 1 and src.dtype not in HALF_DTYPES
-                    and (c * src.element_size()) % 16 == 0 and h * w * c < 2 ** 31 and n <= 65535):
+                    and _chunks_and_offsets(c, h, w, src.element_size()) and n <= 65535):
                 # an NCHW source for a channel-last destination: one tiled transpose (reads and writes in 256-byte runs)
                 # and the channel-last kernel, instead of the NCHW kernel's 4-byte gathers (92 -> 56 us at Wildtrack
                 # size).  NCHW -> NCHW keeps the gather kernel (90 us): transpose + warp_fwd_cl_nchw measured 142 us.
@@ -183,9 +194,9 @@ class WarpPerspectiveFunction(Function):
         (M,) = ctx.saved_tensors
         n, c, h, w, H, W, layout = ctx.geom
         near = layout & NEAREST
-        if grad_out.is_cuda and (c * grad_out.element_size()) % 16 == 0 and h * w * c < 2 ** 31:
+        if grad_out.is_cuda and _chunks_and_offsets(c, h, w, grad_out.element_size()):
             # channel-last on both sides whatever the forward's layouts were: there the gradient is a GATHER over the
-            # destination pixels whose footprint touches each source texel (csrc/warp_perspective.hip: no atomics,
+            # destination pixels whose footprint touches each source texel (csrc/warp_backward.hip: no atomics,
             # deterministic, grad_src written once); NCHW gradients are transposed on the way in / out
             g = grad_out.contiguous() if layout & DST_NHWC else _transpose(grad_out.contiguous(), n, c, H * W)
             grad_src = torch.empty((n, c, h, w), dtype=grad_out.dtype, device=grad_out.device,
