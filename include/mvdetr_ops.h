@@ -677,6 +677,44 @@ int mvdetr_distance_nms_f64(void *stream, const double *points, const double *sc
 const char *mvdetr_detect_last_kernel(void);
 int64_t mvdetr_detect_launch_count(void);
 
+/* ---- Peak extraction: heat map (+ offset, + wh) -> the top_k local maxima of every map ---------------------------------
+ * (csrc/peak_detect.hip; additive entries, the ABI version above is unchanged.)  The reference's ctdet_decode
+ * (utils/decode.py:7-77) for single-channel maps, on the device and without a host round-trip.  Per map b of heatmap
+ * [batch, 1, height, width] (raw logits), offset and wh [batch, 2, height, width] (either may be NULL), all addressed through
+ * their four element strides (host arrays), so channels_last maps are read in place:
+ *   score      s = 1 / (1 + exp(-logit)), one expression evaluated once per cell;
+ *   candidate  a cell whose score equals the maximum of the scores of its 3x3 neighbourhood inside the map (max_pool2d pads
+ *              with -inf), compared on the scores, so a plateau of equal scores is kept whole; with use_thres != 0 also
+ *              s > cls_thres (rounded to the element type).  A NaN score is never a candidate and is ignored in its
+ *              neighbours' maxima (max_pool2d would propagate it: the library's deviation);
+ *   order      score descending, EQUAL SCORES HIGHER ROW-MAJOR CELL INDEX FIRST (the library's tie rule; torch.topk's order
+ *              among ties is unspecified); the first top_k candidates are written, 1 <= top_k <= 1024;
+ *   row        x = column + dx, y = row + dy (one rounded add; 0.5 without an offset map), w and h as gathered, and the box
+ *              x1 = (x - 0.5 w) scale, y1 = (y - h) scale, x2 = (x + 0.5 w) scale, y2 = y scale: the decoded point is the
+ *              foot point, the bottom-centre of the box; every product, sum and difference rounded on its own.
+ * Outputs, all device memory: xy [batch, top_k, 2], wh_out [batch, top_k, 2] and box [batch, top_k, 4] (both NULL when wh
+ * is), score [batch, top_k], cell [batch, top_k] row-major indices, count [batch] the TRUE number of candidates, also when
+ * it exceeds top_k; rows at and after min(count, top_k) are zero.  Correct for any number of candidates from 0 to
+ * height * width (<= 2^30).  workspace: mvdetr_peak_detect_workspace_bytes(batch, height, width, elem_size) bytes, 16-byte
+ * aligned, contents arbitrary.  Two launches, no host synchronisation, no floating-point and no device-scope atomics:
+ * bit-reproducible.  A map's candidate list lives in LDS up to mvdetr_peak_detect_lds_capacity(elem_size) candidates and in
+ * the workspace beyond; the count decides, on the device. */
+int64_t mvdetr_peak_detect_workspace_bytes(int batch, int height, int width, int elem_size);
+int mvdetr_peak_detect_lds_capacity(int elem_size);
+int mvdetr_peak_detect_forward_f32(void *stream, const float *heatmap, const int64_t *heatmap_stride, const float *offset,
+                                   const int64_t *offset_stride, const float *wh, const int64_t *wh_stride, int batch, int height,
+                                   int width, int top_k, double cls_thres, int use_thres, double scale, void *workspace, float *xy,
+                                   float *wh_out, float *box, float *score, int32_t *cell, int32_t *count);
+int mvdetr_peak_detect_forward_f64(void *stream, const double *heatmap, const int64_t *heatmap_stride, const double *offset,
+                                   const int64_t *offset_stride, const double *wh, const int64_t *wh_stride, int batch, int height,
+                                   int width, int top_k, double cls_thres, int use_thres, double scale, void *workspace, double *xy,
+                                   double *wh_out, double *box, double *score, int32_t *cell, int32_t *count);
+/* Name of the route the last device call of this process took: "peak_compact+peak_select", with "_global" appended when any
+ * map of that call kept its list in the workspace ("none" before the first call).  The route is chosen on the device, so this
+ * WAITS for the device and reads one flag back: for tests and tools.  And the number of kernel launches these entries made. */
+const char *mvdetr_peak_detect_last_kernel(void);
+int64_t mvdetr_peak_detect_launch_count(void);
+
 /* ---- CPU path (host pointers, no stream, synchronous) ------------------------------------------------------------
  * The reference extension raises for CPU tensors (ms_deform_attn_cpu.cpp:17-41 are stubs; ms_deform_attn.h:38,60).
  * These entry points make the same contracts work on host memory: same argument meaning and layouts as the device
@@ -759,6 +797,17 @@ int mvdetr_distance_nms_host_f32(const float *points, const float *scores, int n
                                  int32_t *count);
 int mvdetr_distance_nms_host_f64(const double *points, const double *scores, int n, double dist_thres, int top_k, int64_t *keep,
                                  int32_t *count);
+
+/* peak extraction on host memory: same arguments as the device entries without the stream and the workspace, the same
+ * candidate test, arithmetic and tie rule; one thread per map */
+int mvdetr_peak_detect_forward_host_f32(const float *heatmap, const int64_t *heatmap_stride, const float *offset,
+                                        const int64_t *offset_stride, const float *wh, const int64_t *wh_stride, int batch,
+                                        int height, int width, int top_k, double cls_thres, int use_thres, double scale, float *xy,
+                                        float *wh_out, float *box, float *score, int32_t *cell, int32_t *count);
+int mvdetr_peak_detect_forward_host_f64(const double *heatmap, const int64_t *heatmap_stride, const double *offset,
+                                        const int64_t *offset_stride, const double *wh, const int64_t *wh_stride, int batch,
+                                        int height, int width, int top_k, double cls_thres, int use_thres, double scale, double *xy,
+                                        double *wh_out, double *box, double *score, int32_t *cell, int32_t *count);
 
 /* Frame ingest: uint8 camera frames [k, src_h, src_w, 3] (pixels dense: 3 bytes each, src_w of them per row; frame_stride and
  * row_stride in BYTES are free, so a cropped view is read in place) -> out [k, 3, dst_h, dst_w] in NCHW memory, or

@@ -54,6 +54,7 @@ class L1Segment(ctypes.Structure):
 LOSS_MAX_SEGMENTS = 4
 _DETECT = [_vp, _vp, _i64p, _vp, _i64p] + [_i] * 3 + [_d] * 3 + [_i] * 3 + [_vp] * 4
 _NMS = [_vp] * 3 + [_i, _d, _i] + [_vp] * 3
+_PEAK = [_vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + [_i] * 4 + [_d, _i, _d] + [_vp] * 7
 _INGEST = [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp] + [ctypes.c_float] * 6 + [_i] * 6 + [ctypes.c_float, _vp]
 _INGEST_HOST = [_vp, ctypes.c_int64, ctypes.c_int64, _vp] + [_d] * 6 + [_i] * 6 + [_d, _vp]
 _FSEG, _LSEG = ctypes.POINTER(FocalSegment), ctypes.POINTER(L1Segment)
@@ -177,6 +178,14 @@ SIGNATURES = {
     "mvdetr_distance_nms_host_f64": (_NMS[1:6] + _NMS[7:], _i),
     "mvdetr_detect_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_detect_launch_count": ([], ctypes.c_int64),
+    "mvdetr_peak_detect_workspace_bytes": ([_i] * 4, ctypes.c_int64),
+    "mvdetr_peak_detect_lds_capacity": ([_i], _i),
+    "mvdetr_peak_detect_forward_f32": (_PEAK, _i),
+    "mvdetr_peak_detect_forward_f64": (_PEAK, _i),
+    "mvdetr_peak_detect_forward_host_f32": (_PEAK[1:14] + _PEAK[15:], _i),
+    "mvdetr_peak_detect_forward_host_f64": (_PEAK[1:14] + _PEAK[15:], _i),
+    "mvdetr_peak_detect_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_peak_detect_launch_count": ([], ctypes.c_int64),
     "mvdetr_ingest_frames_f32": (_INGEST, _i),
     "mvdetr_ingest_frames_f16": (_INGEST, _i),
     "mvdetr_ingest_frames_bf16": (_INGEST, _i),

@@ -855,6 +855,105 @@ MVDETR_DETECT_HOST_ENTRIES(double, f64)
 
 }  // extern "C"
 
+// ---- peak extraction (csrc/peak_detect.hip's contract on host memory) ---------------------------------------------------------
+// The reference's ctdet_decode (utils/decode.py:7-77) for single-channel maps, one thread per map: scores once into a plane, a
+// cell is a candidate when no neighbour inside the map has a greater score (a NaN is never one and is ignored as a neighbour),
+// the candidates are sorted by (score, cell) descending -- the library's tie rule -- and the first top_k written.  Every product,
+// sum and difference of the box is a separate rounding (baseline x86-64: nothing to contract into).
+namespace {
+
+template <typename T>
+int peak_detect_host(const T *hm, const int64_t *hs, const T *off, const int64_t *os, const T *wh, const int64_t *ws, int B, int H, int W,
+                     int top_k, double cls_thres, int use_thres, double scale_in, T *xy, T *wh_out, T *box, T *score, int32_t *cell,
+                     int32_t *count)
+{
+    if (!hm || !hs || (off && !os) || (wh && (!ws || !wh_out || !box)) || !xy || !score || !cell || !count || B < 1 || H < 1 || W < 1 ||
+        top_k < 1 || top_k > 1024 || (int64_t)H * W > ((int64_t)1 << 30))
+        return 1;
+    const T thres = T(cls_thres), scale = T(scale_in);
+    parallel_ranges(B, [=](int64_t b0, int64_t b1) {
+        std::vector<T> s((size_t)H * W);
+        std::vector<std::pair<T, int>> cand;
+        for (int64_t b = b0; b < b1; ++b) {
+            for (int row = 0; row < H; ++row)
+                for (int col = 0; col < W; ++col)
+                    s[(size_t)row * W + col] = T(1) / (T(1) + std::exp(-hm[b * hs[0] + row * hs[2] + col * hs[3]]));
+            cand.clear();
+            for (int row = 0; row < H; ++row)
+                for (int col = 0; col < W; ++col) {
+                    const T v = s[(size_t)row * W + col];
+                    bool ok = v == v && (!use_thres || v > thres);
+                    for (int dr = -1; dr <= 1 && ok; ++dr)
+                        for (int dc = -1; dc <= 1 && ok; ++dc)
+                            if (row + dr >= 0 && row + dr < H && col + dc >= 0 && col + dc < W)
+                                ok = !(s[(size_t)(row + dr) * W + col + dc] > v);
+                    if (ok) cand.emplace_back(v + T(0), row * W + col);
+                }
+            const int n = (int)cand.size(), m = std::min(n, top_k);
+            std::partial_sort(cand.begin(), cand.begin() + m, cand.end(), [](const std::pair<T, int> &a, const std::pair<T, int> &c) {
+                return a.first > c.first || (a.first == c.first && a.second > c.second);
+            });
+            count[b] = n;
+            for (int r = 0; r < top_k; ++r) {
+                const int64_t at = b * top_k + r;
+                T x = T(0), y = T(0), w = T(0), h = T(0), x1 = T(0), y1 = T(0), x2 = T(0), y2 = T(0);
+                if (r < m) {
+                    const int c = cand[r].second, row = c / W, col = c - row * W;
+                    T dx = T(0.5), dy = T(0.5);
+                    if (off) {
+                        const T *o = off + b * os[0] + row * os[2] + col * os[3];
+                        dx = o[0];
+                        dy = o[os[1]];
+                    }
+                    x = T(col) + dx;
+                    y = T(row) + dy;
+                    if (wh) {
+                        const T *p = wh + b * ws[0] + row * ws[2] + col * ws[3];
+                        w = p[0];
+                        h = p[ws[1]];
+                        const T half = T(0.5) * w, xl = x - half, yt = y - h, xr = x + half;
+                        x1 = xl * scale;
+                        y1 = yt * scale;
+                        x2 = xr * scale;
+                        y2 = y * scale;
+                    }
+                }
+                xy[2 * at] = x;
+                xy[2 * at + 1] = y;
+                score[at] = r < m ? cand[r].first : T(0);
+                cell[at] = r < m ? cand[r].second : 0;
+                if (wh) {
+                    wh_out[2 * at] = w;
+                    wh_out[2 * at + 1] = h;
+                    box[4 * at] = x1;
+                    box[4 * at + 1] = y1;
+                    box[4 * at + 2] = x2;
+                    box[4 * at + 3] = y2;
+                }
+            }
+        }
+    });
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+#define MVDETR_PEAK_HOST_ENTRY(T, SFX)                                                                                            \
+    int mvdetr_peak_detect_forward_host_##SFX(const T *heatmap, const int64_t *heatmap_stride, const T *offset,                    \
+                                              const int64_t *offset_stride, const T *wh, const int64_t *wh_stride, int batch,      \
+                                              int height, int width, int top_k, double cls_thres, int use_thres, double scale,     \
+                                              T *xy, T *wh_out, T *box, T *score, int32_t *cell, int32_t *count)                   \
+    {                                                                                                                            \
+        return peak_detect_host<T>(heatmap, heatmap_stride, offset, offset_stride, wh, wh_stride, batch, height, width, top_k,     \
+                                   cls_thres, use_thres, scale, xy, wh_out, box, score, cell, count);                              \
+    }
+MVDETR_PEAK_HOST_ENTRY(float, f32)
+MVDETR_PEAK_HOST_ENTRY(double, f64)
+
+}  // extern "C"
+
 // ---- frame ingest ----------------------------------------------------------------------------------------------------------
 // uint8 frames -> normalised, resized (and optionally perspective-augmented) float images: the contract of mvdetr_ingest_frames_*
 // in include/mvdetr_ops.h.  Resize taps come from integers (floor and remainder of ((2i + 1) src - dst) / (2 dst)), the

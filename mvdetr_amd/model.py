@@ -22,6 +22,7 @@ from .ops import warp_perspective
 from .ops.conv_winograd import (winograd_conv3x3, winograd_conv3x3_available, winograd_conv3x3_bn_act,
                                 winograd_conv3x3_bn_act_available)
 from .ops.detect import bev_detect
+from .ops.peak_detect import peak_detect, PeakDetections
 from .ops.ingest import ingest_frames
 from .ops.trunk_epilogue import (bn_act, bn_act_half, bn_relu_maxpool, bn_relu_maxpool_half, fused_bn_act_available,
                                   fused_bn_act_half_available, fused_bn_relu_maxpool_available,
@@ -436,6 +437,26 @@ class MVDeTr(nn.Module):
             # 16-bit inference: the extraction is float32 / float64 (thresholds, positions); two small maps are upcast
             world_heatmap, world_offset = world_heatmap.float(), world_offset.float()
         return bev_detect(world_heatmap, world_offset, **detect_kw)
+
+    def detect_views(self, imgs, M, *, view_top_k=100, view_cls_thres=None, **detect_kw):
+        """``detect`` plus the per-view detections of the same forward: ``(Detections, PeakDetections)``.  The first is exactly
+        what ``detect(imgs, M, **detect_kw)`` returns.  The second is the fused peak + top-K decode (ops/peak_detect.py, the
+        reference's ``ctdet_decode`` of trainer.py:173) of the three image-plane maps with ``scale = img_reduce``, so its boxes
+        are pixels of the dataset's ``img_shape`` frame and its points the foot points (frameDataset.py:207-208); every tensor's
+        leading dimension is viewed as ``[B, N, ...]`` and ``count`` as ``[B, N]``.  One ``self(imgs, M)`` under ``no_grad``
+        serves both, through ``__call__`` (hooks see the maps); nothing waits for the GPU.  A ``to_inference`` model's five
+        maps are upcast to float32 first."""
+        B, N = imgs.shape[:2]
+        with torch.no_grad():
+            (world_heatmap, world_offset), (imgs_heatmap, imgs_offset, imgs_wh) = self(imgs, M)
+        detect_kw.setdefault("world_reduce", self.geom.world_reduce)
+        if self.compute_dtype is not None:
+            world_heatmap, world_offset = world_heatmap.float(), world_offset.float()
+            imgs_heatmap, imgs_offset, imgs_wh = imgs_heatmap.float(), imgs_offset.float(), imgs_wh.float()
+        det = bev_detect(world_heatmap, world_offset, **detect_kw)
+        views = peak_detect(imgs_heatmap, imgs_offset, imgs_wh, top_k=view_top_k, cls_thres=view_cls_thres,
+                            scale=self.geom.img_reduce)
+        return det, PeakDetections(*[t.view(B, N, *t.shape[1:]) for t in views])
 
     def hot_path(self, feat, proj):
         """warp + shadow transformer only (the path BASELINE.json's north_star names), for timing."""

@@ -19,4 +19,5 @@ from .conv_winograd import (winograd_conv3x3, winograd_conv3x3_available, winogr
 from .deform_conv import deform_conv2d, DeformConv2d, DeformConv2dFunction  # noqa: E402,F401
 from .attention import attention, MultiheadAttention, AttentionFunction  # noqa: E402,F401
 from .detect import bev_detect, distance_nms, Detections  # noqa: E402,F401
+from .peak_detect import peak_detect, PeakDetections  # noqa: E402,F401
 from .ingest import ingest_frames  # noqa: E402,F401

@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from ..ops.detect import bev_detect, distance_nms
+from ..ops.peak_detect import peak_detect
 
 
 def detection_rows(det, frames):
@@ -38,3 +39,12 @@ def nms_fused(points, scores, dist_thres=50 / 2.5, top_k=50):
     """``nms``'s signature and return types (keep LongTensor, count int) on the library's kernel."""
     keep, count = distance_nms(points, scores, dist_thres, top_k)
     return keep, int(count)
+
+
+def ctdet_decode_fused(heatmap, offset=None, wh=None, top_K=100):
+    """``ctdet_decode``'s tensor ([B, top_K, 3] or [B, top_K, 5]) from the fused kernel (ops/peak_detect.py), single-channel
+    heat maps only, no read-back.  Differs from ``ctdet_decode`` in two places: rows past the map's candidate count are zero
+    (the reference fills them with zero-score cells in ``torch.topk``'s order), and equal scores come higher cell first."""
+    det = peak_detect(heatmap, offset, wh, top_k=top_K)
+    parts = [det.xy] + ([] if wh is None else [det.wh]) + [det.score.unsqueeze(2)]
+    return torch.cat(parts, dim=2)
