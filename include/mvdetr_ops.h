@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel; still 18 with mvdetr_attn_forward_f16 / _bf16 and mvdetr_deform_conv2d_forward_f16 / _bf16 (purely additive) */
+#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel; still 18 with mvdetr_attn_forward_f16 / _bf16 and mvdetr_deform_conv2d_forward_f16 / _bf16 (purely additive), and with the mvdetr_frame_targets_* entries (additive too) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -843,6 +843,46 @@ int mvdetr_ingest_frames_host_f32(const uint8_t *frames, int64_t frame_stride, i
 int mvdetr_ingest_frames_host_f64(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const double *mats, double a0,
                                   double a1, double a2, double b0, double b1, double b2, int k, int src_h, int src_w, int dst_h,
                                   int dst_w, int layout_nhwc, double border, double *out);
+
+/* Training targets: the CenterNet-style ground truth of one SEGMENT of `maps` equally shaped [height, width] maps (the
+ * reference's get_gt, datasets/frameDataset.py:19-46, with the box half of its random_affine, utils/image_utils.py:46-83) from
+ * padded annotations, in one launch; no count is read back, nothing allocates or synchronises.
+ *   coords   [maps, cap, 4] boxes (x1, y1, x2, y2) with is_boxes != 0, else [maps, cap, 2] points (x, y); fp64, at `reduce`
+ *            times the map's resolution
+ *   count    [maps] int32, the valid objects of a map (clamped to [0, cap]); pids [maps, cap] int64 or null (zeros)
+ *   mats     [maps, 9] row-major 3x3 or null, boxes only: the augmentation (source pixel -> destination pixel; its first two
+ *            rows are used); shrink [maps] or null (= 1), with mats only: sqrt(max(|sin a|, |cos a|)) of the rotation angle,
+ *            made by the caller (the kernel has no sin / cos / sqrt); img_h, img_w: the image the boxes are clipped to
+ *   keep     [maps] bytes or null: a map with keep == 0 gets all-zero outputs, heat map included (camera dropout)
+ *   patch    [2 radius + 1, 2 radius + 1] fp32, the gaussian made by the caller (no device exp); radius <= max_radius()
+ *   cap <= 1024, cap <= top_k, height and width <= 16384, maps <= 65535
+ * Arithmetic, fp64 and WITHOUT FMA contraction until the stated roundings, per object in order:
+ *   with mats  each corner (x1,y1) (x2,y2) (x1,y2) (x2,y1) -> X = (M00 x + M01 y) + M02, Y = (M10 x + M11 y) + M12; hull = min /
+ *              max of the four; per axis c = (hi + lo) / 2, s = (hi - lo) shrink, lo' = min(max(c - s / 2, 0), lim), hi' =
+ *              min(max(c + s / 2, 0), lim), lim = img_w - 1 / img_h - 1; with w = hi'x - lo'x, h = hi'y - lo'y, area =
+ *              (x2 - x1)(y2 - y1) the box is kept when w > 4 && h > 4, w h / (area + 1e-16) > 0.1 and
+ *              max(w / (h + 1e-16), h / (w + 1e-16)) < 10.  Kept boxes are compacted in order: slot = rank among the kept.
+ *   without    slot = object index.
+ *   a box's point is x = (x1 + x2) / 2, y = y2, its size w = x2 - x1, h = y2 - y1; centre ct = fp32(x / reduce), fp32(y / reduce)
+ *   (one rounding each); inside when 0 <= ct.x < width && 0 <= ct.y < height on the fp32 values, else the slot stays empty;
+ *   cell = trunc(ct), idx = cell.y width + cell.x, offset = ct - fp32(cell) in fp32, wh = fp32(w / reduce), fp32(h / reduce).
+ * Outputs (EVERY element is written; empty slots and untouched cells are zero): heatmap [maps, height, width] fp32, cell (y, x)
+ * = max of patch[y - cy + radius, x - cx + radius] over the inside objects with |x - cx|, |y - cy| <= radius; reg_mask
+ * [maps, top_k] bytes 0 / 1; idx, pid [maps, top_k] int64; offset [maps, top_k, 2] fp32; wh [maps, top_k, 2] fp32 (boxes:
+ * required; points: null).  The result is bit-reproducible (a gather: no atomics).
+ * mvdetr_frame_targets_launch_count: kernel launches of this process so far (one per call with maps > 0). */
+int mvdetr_frame_targets_f64(void *stream, const double *coords, int is_boxes, const int32_t *count, const int64_t *pids,
+                             const double *mats, const double *shrink, const uint8_t *keep, const float *patch, int maps, int cap,
+                             int height, int width, int img_h, int img_w, int radius, int top_k, double reduce, float *heatmap,
+                             uint8_t *reg_mask, int64_t *idx, int64_t *pid, float *offset, float *wh);
+int mvdetr_frame_targets_max_radius(void);
+int64_t mvdetr_frame_targets_launch_count(void);
+
+/* the same on host memory, synchronous: the same arithmetic operation for operation (threads own maps, then heat-map rows) */
+int mvdetr_frame_targets_host_f64(const double *coords, int is_boxes, const int32_t *count, const int64_t *pids,
+                                  const double *mats, const double *shrink, const uint8_t *keep, const float *patch, int maps,
+                                  int cap, int height, int width, int img_h, int img_w, int radius, int top_k, double reduce,
+                                  float *heatmap, uint8_t *reg_mask, int64_t *idx, int64_t *pid, float *offset, float *wh);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ _NMS = [_vp] * 3 + [_i, _d, _i] + [_vp] * 3
 _PEAK = [_vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + [_i] * 4 + [_d, _i, _d] + [_vp] * 7
 _INGEST = [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp] + [ctypes.c_float] * 6 + [_i] * 6 + [ctypes.c_float, _vp]
 _INGEST_HOST = [_vp, ctypes.c_int64, ctypes.c_int64, _vp] + [_d] * 6 + [_i] * 6 + [_d, _vp]
+_FRAME_TARGETS = [_vp, _vp, _i] + [_vp] * 6 + [_i] * 8 + [_d] + [_vp] * 6
 _FSEG, _LSEG = ctypes.POINTER(FocalSegment), ctypes.POINTER(L1Segment)
 
 SIGNATURES = {
@@ -192,6 +193,10 @@ SIGNATURES = {
     "mvdetr_ingest_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_ingest_frames_host_f32": (_INGEST_HOST, _i),
     "mvdetr_ingest_frames_host_f64": (_INGEST_HOST, _i),
+    "mvdetr_frame_targets_f64": (_FRAME_TARGETS, _i),
+    "mvdetr_frame_targets_host_f64": (_FRAME_TARGETS[1:], _i),
+    "mvdetr_frame_targets_max_radius": ([], _i),
+    "mvdetr_frame_targets_launch_count": ([], ctypes.c_int64),
 }
 
 

@@ -19,8 +19,11 @@
 //   attention    (softmax(q k^T / sqrt(D)) v, strided operands) forward and dQ: threads own query rows and walk the keys 64 at a
 //             time (online softmax; never more than that tile of scores); dK / dV: threads own key rows and walk the queries,
 //             the probabilities recomputed from lse.  Dropout by the shared counter-based hash (attention_hash.h).
+//   frame targets  threads own maps for the slot lists (the compaction of a map is serial), then rows of the heat maps; the
+//             per-object arithmetic is the kernel's own (frame_targets_core.h), uncontracted.
 #include "../../include/mvdetr_ops.h"
 #include "attention_hash.h"
+#include "frame_targets_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1072,6 +1075,80 @@ int mvdetr_ingest_frames_host_f64(const uint8_t *frames, int64_t frame_stride, i
 {
     const double a[3] = {a0, a1, a2}, b[3] = {b0, b1, b2};
     return ingest_host<double>(frames, frame_stride, row_stride, mats, a, b, k, src_h, src_w, dst_h, dst_w, layout_nhwc, border, out);
+}
+
+}  // extern "C"
+
+// ---- training targets ------------------------------------------------------------------------------------------------------
+// The host twin of frame_targets.hip: the contract of mvdetr_frame_targets_* on host memory, the per-object arithmetic shared
+// with the kernel (frame_targets_core.h; this file is built with -ffp-contract=off).  Threads own maps for the slot lists, then
+// rows of the heat maps.
+extern "C" {
+
+int mvdetr_frame_targets_host_f64(const double *coords, int is_boxes, const int32_t *count, const int64_t *pids, const double *mats,
+                                  const double *shrink, const uint8_t *keep, const float *patch, int maps, int cap, int height,
+                                  int width, int img_h, int img_w, int radius, int top_k, double reduce, float *heatmap,
+                                  uint8_t *reg_mask, int64_t *idx, int64_t *pid, float *offset, float *wh)
+{
+    if (maps < 0 || maps > 65535 || cap < 1 || cap > MVDETR_FT_MAX_CAP || top_k < cap || height < 1 || width < 1 ||
+        height > MVDETR_FT_MAX_DIM || width > MVDETR_FT_MAX_DIM || radius < 0 || radius > MVDETR_FT_MAX_RADIUS || !(reduce > 0.0))
+        return 1;
+    if ((!is_boxes && (mats || wh)) || (is_boxes && !wh) || (!mats && shrink) || (mats && (img_h < 1 || img_w < 1))) return 1;
+    if (maps == 0) return 0;
+    if (!coords || !count || !patch || !heatmap || !reg_mask || !idx || !pid || !offset) return 1;
+    const int H = height, W = width, r = radius, side = 2 * r + 1;
+    std::vector<int> centres((size_t)maps * cap * 2), filled(maps);          // per map: (cx, cy) of its slots, cx = -1: empty
+    parallel_ranges(maps, [&](int64_t m0, int64_t m1) {
+        for (int64_t m = m0; m < m1; ++m) {
+            int n = std::min(std::max(count[m], 0), cap), used = 0;
+            if (keep && !keep[m]) n = 0;
+            int *cen = centres.data() + m * cap * 2;
+            for (int i = 0; i < n; ++i) {
+                const int64_t at = m * cap + i;
+                double x, y, w = 0, h = 0;
+                if (is_boxes) {
+                    double b[4] = {coords[at * 4], coords[at * 4 + 1], coords[at * 4 + 2], coords[at * 4 + 3]};
+                    if (mats && !ft_move_box(b, mats + m * 9, shrink ? shrink[m] : 1.0, (double)(img_w - 1), (double)(img_h - 1), b))
+                        continue;
+                    x = (b[0] + b[2]) / 2, y = b[3], w = b[2] - b[0], h = b[3] - b[1];
+                } else {
+                    x = coords[at * 2], y = coords[at * 2 + 1];
+                }
+                const FtSlot s = ft_slot(x, y, w, h, reduce, H, W);
+                const int64_t o = m * top_k + used;
+                cen[used * 2] = s.inside ? s.cx : -1;
+                cen[used * 2 + 1] = s.cy;
+                reg_mask[o] = s.inside ? 1 : 0;
+                idx[o] = s.inside ? (int64_t)s.cy * W + s.cx : 0;
+                pid[o] = s.inside && pids ? pids[at] : 0;
+                offset[o * 2] = s.off_x, offset[o * 2 + 1] = s.off_y;
+                if (wh) wh[o * 2] = s.wh_x, wh[o * 2 + 1] = s.wh_y;
+                ++used;
+            }
+            for (int64_t o = m * top_k + used; o < (m + 1) * top_k; ++o) {
+                reg_mask[o] = 0, idx[o] = 0, pid[o] = 0;
+                offset[o * 2] = offset[o * 2 + 1] = 0.f;
+                if (wh) wh[o * 2] = wh[o * 2 + 1] = 0.f;
+            }
+            filled[m] = used;
+        }
+    });
+    parallel_ranges((int64_t)maps * H, [&](int64_t r0, int64_t r1) {
+        for (int64_t row = r0; row < r1; ++row) {
+            const int64_t m = row / H;
+            const int y = (int)(row - m * H);
+            float *out = heatmap + row * W;
+            std::fill(out, out + W, 0.f);
+            const int *cen = centres.data() + m * cap * 2;
+            for (int s = 0; s < filled[m]; ++s) {
+                const int cx = cen[s * 2], dy = y - cen[s * 2 + 1];
+                if (cx < 0 || dy < -r || dy > r) continue;
+                const float *p = patch + (dy + r) * side;
+                for (int x = std::max(cx - r, 0); x <= std::min(cx + r, W - 1); ++x) out[x] = std::max(out[x], p[x - cx + r]);
+            }
+        }
+    });
+    return 0;
 }
 
 }  // extern "C"

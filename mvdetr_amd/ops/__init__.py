@@ -21,3 +21,4 @@ from .attention import attention, MultiheadAttention, AttentionFunction  # noqa:
 from .detect import bev_detect, distance_nms, Detections  # noqa: E402,F401
 from .peak_detect import peak_detect, PeakDetections  # noqa: E402,F401
 from .ingest import ingest_frames  # noqa: E402,F401
+from .targets import map_targets  # noqa: E402,F401

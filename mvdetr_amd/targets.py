@@ -1,7 +1,11 @@
-"""Training targets (host, numpy): the CenterNet-style ground truth MVDeTr's dataset builds for every map
-(reference: datasets/frameDataset.py:19-46 with the gaussian of utils/image_utils.py:86-111), and seeded synthetic frames
-of them for tests and tools (this package has no dataset classes)."""
+"""Training targets: the CenterNet-style ground truth MVDeTr's dataset builds for every map (reference:
+datasets/frameDataset.py:19-46 with the gaussian of utils/image_utils.py:86-111).  ``get_gt`` is the host (numpy) definition, one
+map at a time; ``frame_targets`` builds the same dicts for whole frames from padded annotation tensors where those live -- on the
+device in two launches of ops.map_targets, with no per-object host work.  Seeded synthetic frames of both serve tests and tools
+(this package has no dataset classes)."""
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -88,3 +92,62 @@ def synthetic_frame_targets(geom, n_people, seed=0, batch=1, top_k=100, world_ke
     world_gt = {k: torch.stack([w[k] for w in world]) for k in world[0]}
     imgs_gt = {k: torch.stack([v[k] for v in views]) for k in views[0]}
     return world_gt, imgs_gt
+
+
+class FrameAnnotations(NamedTuple):
+    """The padded annotations of ``B`` frames that ``frame_targets`` takes, in its argument order (``*annotations``).  Rows past
+    a count are padding and never read; the tensors may live on the device for a whole run."""
+    world_pts: torch.Tensor          # [B, cap, 2] float64 (x, y) on the ground grid
+    world_count: torch.Tensor        # [B] int32
+    boxes: torch.Tensor              # [B, N, cap, 4] float64 (x1, y1, x2, y2) in image pixels
+    box_count: torch.Tensor          # [B, N] int32
+    world_pids: torch.Tensor         # [B, cap] int64
+    box_pids: torch.Tensor           # [B, N, cap] int64
+
+
+def frame_targets(geom, world_pts, world_count, boxes, box_count, world_pids=None, box_pids=None, *, M=None, angles=None,
+                  keep_cams=None, top_k=100, world_kernel_size=10, img_kernel_size=10):
+    """(world_gt, imgs_gt) of ``B`` frames as a dataloader collates them -- world_gt[key]: [B, ...], imgs_gt[key]: [B, N, ...],
+    'wh' only there: the layout MVDeTrCriterion takes -- from padded annotations (FrameAnnotations), built where they live by
+    two ops.map_targets calls: one launch for the B world maps, one for the B N view maps.
+
+    ``M`` [B, N, 3, 3] (the matrices augment.random_affine returns; CPU or device) moves the boxes as augment.affine_boxes
+    does, with the rotation ``angles`` [B, N] in degrees; ``keep_cams`` [B, N] bool zeroes the view targets of dropped cameras
+    and nothing else (the reference's camera dropout, frameDataset.py:226-231).  The world points are not augmented."""
+    from .ops import map_targets
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 4:
+        raise RuntimeError(f"frame_targets: boxes must be [B, N, cap, 4], got {tuple(getattr(boxes, 'shape', ()))}")
+    B, N = boxes.shape[:2]
+    per_map = lambda t: None if t is None else t.flatten(0, 1)  # noqa: E731
+    world_gt = map_targets(geom.Rworld_shape, points=world_pts, count=world_count, pids=world_pids, reduce=geom.world_reduce,
+                           kernel_size=world_kernel_size, top_k=top_k)
+    views = map_targets(geom.Rimg_shape, boxes=per_map(boxes), count=per_map(box_count), pids=per_map(box_pids), M=per_map(M),
+                        angle=per_map(angles), img_hw=geom.img_shape, keep=per_map(keep_cams), reduce=geom.img_reduce,
+                        kernel_size=img_kernel_size, top_k=top_k)
+    return world_gt, {k: v.unflatten(0, (B, N)) for k, v in views.items()}
+
+
+def synthetic_frame_annotations(geom, n_people, seed=0, batch=1, cap=None):
+    """The FrameAnnotations (CPU) of the frames synthetic_frame_targets draws: the same rng, the same draws in the same order,
+    so ``frame_targets(geom, *synthetic_frame_annotations(...))`` is ``synthetic_frame_targets(...)``.  A view's box is
+    (x - w / 2, y - h, x + w / 2, y) around its drawn foot point (x, y): the point and size formed back from it agree with the
+    draws to an fp64 ulp, which the targets' fp32 roundings absorb.  ``cap`` (default n_people) pads the object axis."""
+    cap = max(n_people, 1) if cap is None else int(cap)
+    if cap < n_people:
+        raise ValueError(f"cap = {cap} cannot hold {n_people} people")
+    rng = np.random.default_rng(seed)
+    gh, gw = geom.worldgrid_shape
+    ih, iw = geom.img_shape
+    N = geom.num_cam
+    pts, boxes = np.zeros((batch, cap, 2)), np.zeros((batch, N, cap, 4))
+    for b in range(batch):
+        pts[b, :n_people, 0], pts[b, :n_people, 1] = rng.uniform(0, gw, n_people), rng.uniform(0, gh, n_people)
+        for c in range(N):
+            w, h = rng.uniform(20, iw / 6, n_people), rng.uniform(40, ih / 3, n_people)
+            x, y = rng.uniform(-0.05 * iw, 1.05 * iw, n_people), rng.uniform(-0.05 * ih, 1.05 * ih, n_people)
+            boxes[b, c, :n_people] = np.stack([x - w / 2, y - h, x + w / 2, y], axis=1)
+    ids = torch.zeros(cap, dtype=torch.int64)
+    ids[:n_people] = torch.arange(n_people)
+    return FrameAnnotations(torch.from_numpy(pts), torch.full((batch,), n_people, dtype=torch.int32), torch.from_numpy(boxes),
+                            torch.full((batch, N), n_people, dtype=torch.int32), ids.expand(batch, cap).contiguous(),
+                            ids.expand(batch, N, cap).contiguous())

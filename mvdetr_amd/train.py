@@ -1,7 +1,8 @@
 """The training objective and one training step (the reference's trainer.py:44-73 without its loop, logging and
 schedules).  On CUDA fp32 / fp64 head outputs the whole objective is two launches of csrc/detection_loss.hip forward (both
 heat maps in one focal launch; world offset, image offset and image wh in one L1 launch) and two backward, with no host
-synchronise; elsewhere, or with the switch of loss/losses.py off, it is the torch composition of the same formulas."""
+synchronise; elsewhere, or with the switch of loss/losses.py off, it is the torch composition of the same formulas.
+``train_step_frames`` is the step from decoded frames and device-resident annotations: ingest and targets on the device too."""
 from __future__ import annotations
 
 import torch
@@ -67,3 +68,16 @@ def train_step(model, criterion, optimizer, imgs, M, world_gt, imgs_gt):
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+def train_step_frames(model, criterion, optimizer, frames_u8, M, annotations, angles=None, keep_cams=None):
+    """One training step from decoded frames: ``model.ingest(frames_u8, M)`` (uint8 [B, N, Hs, Ws, 3] -> the augmented,
+    normalised trunk input), the targets of ``annotations`` (targets.FrameAnnotations, or its first four to six tensors) moved
+    by the same ``M`` -- targets.frame_targets on the model's device: two launches, no per-object host work; annotations that
+    already live there are used in place -- then ``train_step``.  ``angles`` [B, N] are the rotations that went into ``M``,
+    ``keep_cams`` [B, N] the camera dropout of the view targets.  Returns the loss tensor; nothing here waits for the device."""
+    from .targets import frame_targets
+    imgs = model.ingest(frames_u8, M)
+    there = lambda t: None if t is None else _on(t, imgs)  # noqa: E731
+    world_gt, imgs_gt = frame_targets(model.geom, *(there(a) for a in annotations), M=M, angles=angles, keep_cams=there(keep_cams))
+    return train_step(model, criterion, optimizer, imgs, M, world_gt, imgs_gt)
