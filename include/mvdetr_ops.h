@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel; still 18 with mvdetr_attn_forward_f16 / _bf16 and mvdetr_deform_conv2d_forward_f16 / _bf16 (purely additive), and with the mvdetr_frame_targets_* entries (additive too) */
+#define MVDETR_OPS_ABI_VERSION 18   /* 12: + mvdetr_warp_perspective_backward_tagged_*; 13: + mvdetr_msda_set_backward_deterministic; the fused training pair takes every encoder shape; 14: + mvdetr_msda_get_backward_deterministic; 15: + mvdetr_deform_conv2d_*; 16: + mvdetr_attention_*; still 16 with mvdetr_bn_act_f32, mvdetr_bn_relu_maxpool_f32, mvdetr_trunk_* and with mvdetr_focal_loss_*, mvdetr_reg_l1_loss_*, mvdetr_loss_* (purely additive: nothing existing changed, and the loader looks every symbol up by name, so a stale build still fails to load); 17: + mvdetr_msda_last_backward_route; still 17 with mvdetr_bn_act_f16 / _bf16 and mvdetr_bn_relu_maxpool_f16 / _bf16, and with mvdetr_winograd_*, mvdetr_conv3x3_winograd_f32 (purely additive again); 18: + mvdetr_add_layernorm_last_kernel; still 18 with mvdetr_attn_forward_f16 / _bf16 and mvdetr_deform_conv2d_forward_f16 / _bf16 (purely additive), and with the mvdetr_frame_targets_* entries (additive too), and with mvdetr_deform_conv2d_route_kind, mvdetr_attention_route_kind (additive) */
 
 /* ABI version of the loaded library (checked by the Python loader). */
 int mvdetr_ops_abi_version(void);
@@ -481,7 +481,9 @@ int mvdetr_transpose_f64(void *stream, const double *src, int n, int rows, int c
  * computed here.  Results are not bit-reproducible run to run (atomics).
  * fp32 calls with a channel-last input, offset_groups 1, in_channels % 16 == 0, out_channels % 32 == 0 and a 16-byte aligned
  * input run the MFMA implicit-GEMM kernels ("dc_fwd_mfma" / "dc_bwd_mfma"); every other call the generic kernels
- * ("dc_fwd_generic" / "dc_bwd_generic").  Return 0, hipErrorInvalidValue or the launch's HIP error. */
+ * ("dc_fwd_generic" / "dc_bwd_generic").  Which one is decided in ONE place, dc_route() of csrc/deform_conv_route.h, for these
+ * and the 16-bit entries below; mvdetr_deform_conv2d_route_kind asks it.  Return 0, hipErrorInvalidValue, hipErrorNotSupported
+ * (an MFMA forward of more than 65535 * 128 output channels) or the launch's HIP error. */
 int mvdetr_deform_conv2d_forward_f32(void *stream, const float *input, const float *offset, const float *weight,
                                      const float *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
                                      int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
@@ -502,6 +504,14 @@ int mvdetr_deform_conv2d_backward_f64(void *stream, const double *grad_out, cons
                                       double *grad_weight);
 /* Name of the kernel route the last deformable-convolution call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_deform_conv2d_last_kernel(void);
+/* The route of a call without making it (an addition, the ABI version above is unchanged): entry 0 = forward, 1 = backward (elem_size 4 or 8), 2 = the 16-bit forward
+ * (elem_size 2); every pointer counts as given, `aligned` != 0 as 16-byte aligned, out_batch_stride as large enough.  Returns the
+ * kind -- 0 dc_fwd_generic, 1 dc_fwd_mfma, 2 dc_fwd_mfma_half, 3 dc_bwd_generic, 4 dc_bwd_mfma, 5 a backward that only zeroes
+ * its outputs -- or minus the status: -1 an empty call (returns 0, launches nothing), -2 hipErrorInvalidValue, -3
+ * hipErrorNotSupported. */
+int mvdetr_deform_conv2d_route_kind(int entry, int elem_size, int batch, int in_channels, int in_h, int in_w, int out_channels,
+                                    int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                    int dil_w, int offset_groups, int input_nhwc, int aligned);
 
 /* 16-bit inference forward (float16 / bfloat16 as raw 16-bit words; 16-bit storage, fp32 arithmetic, ONE rounding on the way
  * out): "dc_fwd_mfma_half", the implicit GEMM of dc_fwd_mfma on v_mfma_f32_32x32x16_{f16,bf16} (csrc/deform_conv_half.hip).
@@ -581,6 +591,13 @@ int mvdetr_attn_forward_bf16(void *stream, const uint16_t *q, const uint16_t *k,
 int mvdetr_attn_half_set_query_tile(int queries);
 /* Name of the kernel route the last device attention call of this process took (any thread). Static; never NULL. */
 const char *mvdetr_attention_last_kernel(void);
+/* The route of a call without making it (an addition, the ABI version above is unchanged; the one decision is attn_route() of csrc/attention_route.h): entry 0 = forward,
+ * 1 = backward (elem_size 4 or 8), 2 = the 16-bit forward (elem_size 2); every pointer counts as given, `aligned` != 0 as all of
+ * them 16-byte aligned, `strides_ok` != 0 as every stride a multiple of 4 (16-bit: 8) elements.  Returns the kind -- 0
+ * attn_fwd_generic, 1 attn_fwd_mfma, 2 attn_fwd_mfma_half, 3 attn_bwd_generic, 4 attn_bwd_mfma -- or minus the status: -1 an
+ * empty call (returns 0, launches nothing), -2 hipErrorInvalidValue, -3 hipErrorNotSupported. */
+int mvdetr_attention_route_kind(int entry, int elem_size, int batch, int heads, int sq, int sk, int head_dim, double dropout_p,
+                                int strides_ok, int aligned);
 
 /* ---- Detection objective: focal loss over heat maps, masked L1 at gathered positions ------------------------------
  * (csrc/detection_loss.hip; additive entries, the ABI version above is unchanged.)  The formulas are those of the

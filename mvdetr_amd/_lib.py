@@ -8,6 +8,7 @@ the CPU run the same library's own host path (csrc/host_path.cpp -- where the re
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import subprocess
 
@@ -133,6 +134,7 @@ SIGNATURES = {
     "mvdetr_warp_perspective_backward_host_f32": (_WARP_HOST, _i),
     "mvdetr_warp_perspective_backward_host_f64": (_WARP_HOST, _i),
     "mvdetr_deform_conv2d_last_kernel": ([], ctypes.c_char_p),
+    "mvdetr_deform_conv2d_route_kind": ([_i] * 18, _i),
     "mvdetr_deform_conv2d_forward_f32": (_DC_FWD, _i),
     "mvdetr_deform_conv2d_forward_f64": (_DC_FWD, _i),
     "mvdetr_deform_conv2d_forward_f16": (_DC_FWD_HALF, _i),
@@ -145,6 +147,7 @@ SIGNATURES = {
     "mvdetr_deform_conv2d_backward_host_f64": (_DC_BWD[1:], _i),
     "mvdetr_attention_last_kernel": ([], ctypes.c_char_p),
     "mvdetr_attention_workspace_bytes": ([_i] * 6, ctypes.c_int64),
+    "mvdetr_attention_route_kind": ([_i] * 7 + [_d, _i, _i], _i),
     "mvdetr_attention_forward_f32": (_ATTN_FWD, _i),
     "mvdetr_attention_forward_f64": (_ATTN_FWD, _i),
     "mvdetr_attn_forward_f16": ([_vp] * 4 + [_i64p] + [_i] * 5 + [_vp], _i),
@@ -199,6 +202,13 @@ SIGNATURES = {
     "mvdetr_frame_targets_launch_count": ([], ctypes.c_int64),
 }
 
+# mvdetr_deform_conv2d_route_kind / mvdetr_attention_route_kind (include/mvdetr_ops.h): the entries, and the kinds in the order of
+# DcKind (csrc/deform_conv_route.h) and AttnKind (csrc/attention_route.h); a refused or empty call answers minus ROUTE_STATUS's index
+ROUTE_FORWARD, ROUTE_BACKWARD, ROUTE_FORWARD_HALF = 0, 1, 2
+DC_KINDS = ("fwd_generic", "fwd_mfma", "fwd_mfma_half", "bwd_generic", "bwd_mfma", "bwd_zero_fill")
+ATTN_KINDS = ("fwd_generic", "fwd_mfma", "fwd_mfma_half", "bwd_generic", "bwd_mfma")
+ROUTE_STATUS = ("ok", "empty", "invalid_value", "not_supported")
+
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 with hipcc (cross-compiles without a GPU)."""
@@ -234,6 +244,22 @@ def lib() -> ctypes.CDLL:
             raise ImportError(f"{LIB_PATH}: ABI version {got}, expected {ABI_VERSION} (stale build?)")
         _lib = handle
     return _lib
+
+
+# (cached: the route is a pure function of these integers, and a dictionary look-up costs a fraction of the foreign call on a
+# path that is taken once per forward)
+@functools.lru_cache(maxsize=1024)
+def dc_route(entry: int, elem_size: int, *args) -> str:
+    """mvdetr_deform_conv2d_route_kind by name: one of DC_KINDS, or of ROUTE_STATUS for a call that launches nothing."""
+    kind = lib().mvdetr_deform_conv2d_route_kind(entry, elem_size, *args)
+    return DC_KINDS[kind] if kind >= 0 else ROUTE_STATUS[-kind]
+
+
+@functools.lru_cache(maxsize=1024)
+def attn_route(entry: int, elem_size: int, *args) -> str:
+    """mvdetr_attention_route_kind by name: one of ATTN_KINDS, or of ROUTE_STATUS for a call that launches nothing."""
+    kind = lib().mvdetr_attention_route_kind(entry, elem_size, *args)
+    return ATTN_KINDS[kind] if kind >= 0 else ROUTE_STATUS[-kind]
 
 
 def check(rc: int, what: str) -> None:

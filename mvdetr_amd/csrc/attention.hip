@@ -27,28 +27,13 @@
 // mvdetr_attn_hash(seed, ((b H + h) Sq + i) Sk + j) >= p 2^32 (attention_hash.h); kept probabilities are scaled by
 // 1 / (1 - p) in the P V product only, lse uses the undropped probabilities, the backward applies the same mask to dO V^T.
 #include "../../include/mvdetr_ops.h"
-#include "attention_hash.h"
-#include "common.h"
+#include "attention.h"
+#include "half_mfma.h"
 
-#include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <initializer_list>
 #include <type_traits>
 
 namespace mvdetr {
-
-std::atomic<const char *> g_attn_last_kernel{"none"};          // (attention_half.hip sets it too)
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-struct AttnP {
-    int B, H, Sq, Sk, D;
-    int64_t q[3], k[3], v[3], o[3], go[3], dq[3], dk[3], dv[3];     // element strides: batch, head, token
-    uint32_t thresh;                                                 // dropout: keep iff hash >= thresh
-    uint64_t seed;
-    double inv_keep;                                                 // 1 / (1 - p)
-};
 
 template <typename T> __device__ __forceinline__ T attn_exp(T x);
 template <> __device__ __forceinline__ float attn_exp<float>(float x) { return expf(x); }
@@ -81,8 +66,6 @@ __global__ __launch_bounds__(256) void attn_delta(const T *__restrict__ go, cons
 }
 
 // ---- generic kernels ------------------------------------------------------------------------------------------------------
-
-constexpr int ATTN_GD = 256;        // largest head dimension of the generic kernels
 
 template <typename T> __device__ __forceinline__ T attn_dot(const T *__restrict__ a, const T *__restrict__ b, int D)
 {
@@ -302,15 +285,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_generic(const T *__restrict_
 // ---- MFMA kernels (fp32, D = 16 or 32) ------------------------------------------------------------------------------------
 //
 // v_mfma_f32_32x32x2_f32: D[i][j] += A[i][k] B[k][j], k = 0, 1.  Lane (r = lane & 31, h = lane >> 5) supplies A[r][h] and
-// B[h][r] and holds D[crow(e, h)][r] in accumulator register e, crow(e, h) = (e & 3) + 8 (e >> 2) + 4 h.  The contraction
+// B[h][r] and holds D[crow(e, h)][r] in accumulator register e, crow = mfma_crow (half_mfma.h).  The contraction
 // index of a step is free as long as A and B agree on it:
 //   "row" products (contraction over the channel):   half h takes channels h D/2 + step (D/2 contiguous floats of its row);
 //   "col" products (contraction over the 32 rows of a tile):  step s of half h takes row crow(s, h) -- the row whose value the
 //   lane holds in register s of a previous product -- and the transposed LDS image stores row x at column tpos(x) = 16 h + s.
 
-constexpr int ATTN_TQ = 128;        // queries (or keys, in the dK / dV kernel) per workgroup: 4 waves x 32
-
-__device__ __forceinline__ int attn_crow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 __device__ __forceinline__ int attn_tpos(int x) { return 16 * ((x >> 2) & 1) + (x & 3) + 4 * (x >> 3); }
 
 // acc += rows_lds (this lane's row: D/2 contiguous floats) x breg
@@ -454,7 +434,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const float *__restrict__ q
             if (key0 + 32 > p.Sk) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
-                    if (key0 + attn_crow(e, h) >= p.Sk) s[e] = -INFINITY;
+                    if (key0 + mfma_crow(e, h) >= p.Sk) s[e] = -INFINITY;
             }
             float mx = s[0];
 #pragma unroll
@@ -475,7 +455,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const float *__restrict__ q
             if (DROP) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
-                    s[e] = attn_keep(p, b, hd, qv ? qi : 0, key0 + attn_crow(e, h)) ? s[e] * inv_keep : 0.f;
+                    s[e] = attn_keep(p, b, hd, qv ? qi : 0, key0 + mfma_crow(e, h)) ? s[e] * inv_keep : 0.f;
             }
             attn_mfma_col(&sVt[buf][ks][r & (D - 1)][16 * h], s, o);
         }
@@ -560,7 +540,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma(const float *__restrict_
             attn_mfma_row<KS>(&sV[r][h * KS], gr, dp);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int key = kt * 32 + attn_crow(e, h);
+                const int key = kt * 32 + mfma_crow(e, h);
                 const float pv = key < p.Sk ? __builtin_amdgcn_exp2f(s[e] * c2 - l2) : 0.f;
                 float d = dp[e];
                 if (DROP) d = attn_keep(p, b, hd, qc, key) ? d * inv_keep : 0.f;
@@ -635,7 +615,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma(const float *__restrict
             attn_mfma_row<KS>(&sG[r][h * KS], vr, dp);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int qi = qt * 32 + attn_crow(e, h);
+                const int qi = qt * 32 + mfma_crow(e, h);
                 const float pv = qi < p.Sq ? __builtin_amdgcn_exp2f(s[e] * c2 - sL[16 * h + e]) : 0.f;
                 float d = dp[e], pd = pv;
                 if (DROP) {
@@ -655,127 +635,95 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma(const float *__restrict
     attn_store_acc<D>(gv + b * p.dv[0] + hd * p.dv[1] + kj * p.dv[2], av, h, 1.f);
 }
 
-// ---- entries --------------------------------------------------------------------------------------------------------------
+// ---- launchers and the entry path: one AttnCall, attn_route(), a switch on the route's kind ---------------------------------
 
-static bool attn_params(const int64_t *strides, int nstr, int B, int H, int Sq, int Sk, int D, double dropout_p,
-                        uint64_t seed, AttnP &p)
+static std::atomic<const char *> g_attn_last_kernel{"none"};
+
+static dim3 attn_dim3(const AttnGrid &g) { return dim3(g.x, g.y, g.z); }
+
+// f(bool_constant<DROP>) for the route's dropout flag; f(integral_constant<int, D>, bool_constant<DROP>) for an MFMA route
+template <typename F> static void attn_for_drop(const AttnRoute &r, F f)
 {
-    if (!strides || B < 0 || H < 0 || Sq < 0 || Sk < 1 || D < 1 || !(dropout_p >= 0.0) || !(dropout_p < 1.0)) return false;
-    p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
-    int64_t *dst[8] = {p.q, p.k, p.v, p.o, p.go, p.dq, p.dk, p.dv};
-    for (int i = 0; i < 8; ++i)
-        for (int j = 0; j < 3; ++j) dst[i][j] = i < nstr ? strides[3 * i + j] : 0;
-    p.thresh = mvdetr_attn_threshold(dropout_p);
-    p.seed = seed;
-    p.inv_keep = 1.0 / (1.0 - dropout_p);
-    return true;
+    if (r.drop) f(std::true_type());
+    else f(std::false_type());
+}
+template <typename F> static void attn_for_mfma(const AttnRoute &r, F f)
+{
+    attn_for_drop(r, [&](auto drop) {
+        if (r.D == 16) f(std::integral_constant<int, 16>(), drop);
+        else f(std::integral_constant<int, 32>(), drop);
+    });
 }
 
-static bool attn_strides_ok(const int64_t *s) { return s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0; }
-
-// the MFMA route: fp32, D 16 or 32, float4 access to every row, a grid that fits
-template <typename T> static bool attn_fast(const AttnP &p, std::initializer_list<const void *> ptrs, int ntensors)
+// every kind of the fp32 / fp64 entries; the backward's after attn_delta
+template <typename T> static int attn_launch(const AttnCall &c)
 {
-    if constexpr (!std::is_same<T, float>::value) return false;
-    if (p.D != 16 && p.D != 32) return false;
-    if (p.H > 65535 || p.B > 65535) return false;
-    for (const void *q : ptrs)
-        if (!aligned(q, 16)) return false;
-    const int64_t *all[8] = {p.q, p.k, p.v, p.o, p.go, p.dq, p.dk, p.dv};
-    for (int i = 0; i < ntensors; ++i)
-        if (!attn_strides_ok(all[i])) return false;
-    return true;
-}
-
-static unsigned attn_rows_grid(int64_t rows) { return (unsigned)std::min<int64_t>((rows + 3) / 4, 1 << 20); }
-
-template <typename T>
-static int attn_forward(void *stream, const T *q, const T *k, const T *v, const int64_t *strides, int B, int H, int Sq, int Sk,
-                        int D, double dropout_p, uint64_t seed, T *out, T *lse)
-{
-    AttnP p;
-    if (!attn_params(strides, 4, B, H, Sq, Sk, D, dropout_p, seed, p)) return (int)hipErrorInvalidValue;
-    const int64_t rows = (int64_t)B * H * Sq;
-    if (rows == 0) return 0;
-    if (!q || !k || !v || !out || !lse) return (int)hipErrorInvalidValue;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool drop = p.thresh != 0;
-    if (attn_fast<T>(p, {q, k, v, out}, 4)) {
-        const dim3 grid((unsigned)((Sq + ATTN_TQ - 1) / ATTN_TQ), (unsigned)H, (unsigned)B);
-#define MVDETR_ATTN_FWD(DD, DR)                                                                                              \
-    hipLaunchKernelGGL((attn_fwd_mfma<DD, DR>), grid, dim3(512), 0, st, (const float *)q, (const float *)k, (const float *)v, \
-                       (float *)out, (float *)lse, p)
-        if (D == 16) { if (drop) MVDETR_ATTN_FWD(16, true); else MVDETR_ATTN_FWD(16, false); }
-        else         { if (drop) MVDETR_ATTN_FWD(32, true); else MVDETR_ATTN_FWD(32, false); }
-#undef MVDETR_ATTN_FWD
-        g_attn_last_kernel = "attn_fwd_mfma";
-    } else {
-        if (D > ATTN_GD) return (int)hipErrorInvalidValue;
-        if (drop)
-            hipLaunchKernelGGL((attn_fwd_generic<T, true>), dim3(attn_rows_grid(rows)), dim3(256), 0, st, q, k, v, out, lse, p);
-        else
-            hipLaunchKernelGGL((attn_fwd_generic<T, false>), dim3(attn_rows_grid(rows)), dim3(256), 0, st, q, k, v, out, lse, p);
-        g_attn_last_kernel = "attn_fwd_generic";
-    }
-    return (int)hipGetLastError();
-}
-
-template <typename T>
-static int attn_backward(void *stream, const T *go, const T *q, const T *k, const T *v, const T *out, const T *lse,
-                         const int64_t *strides, int B, int H, int Sq, int Sk, int D, double dropout_p, uint64_t seed,
-                         void *workspace, T *gq, T *gk, T *gv)
-{
-    AttnP p;
-    if (!attn_params(strides, 8, B, H, Sq, Sk, D, dropout_p, seed, p)) return (int)hipErrorInvalidValue;
-    const int64_t rows = (int64_t)B * H * Sq, krows = (int64_t)B * H * Sk;
-    if (B * H == 0) return 0;
-    if (!k || !v || !gk || !gv || (rows && (!go || !q || !out || !lse || !gq || !workspace))) return (int)hipErrorInvalidValue;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool drop = p.thresh != 0;
-    T *delta = static_cast<T *>(workspace);
-    if (rows)
-        hipLaunchKernelGGL((attn_delta<T>), dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 1 << 20)), dim3(256), 0, st, go,
-                           out, delta, p);
-    if (rows && attn_fast<T>(p, {go, q, k, v, gq, gk, gv}, 8)) {
-        const dim3 gq_grid((unsigned)((Sq + ATTN_TQ - 1) / ATTN_TQ), (unsigned)H, (unsigned)B);
-        const dim3 gk_grid((unsigned)((Sk + ATTN_TQ - 1) / ATTN_TQ), (unsigned)H, (unsigned)B);
-#define MVDETR_ATTN_BWD(DD, DR)                                                                                              \
-    do {                                                                                                                     \
-        hipLaunchKernelGGL((attn_bwd_dq_mfma<DD, DR>), gq_grid, dim3(256), 0, st, (const float *)go, (const float *)q,       \
-                           (const float *)k, (const float *)v, (const float *)lse, (const float *)delta, (float *)gq, p);    \
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma<DD, DR>), gk_grid, dim3(256), 0, st, (const float *)go, (const float *)q,      \
-                           (const float *)k, (const float *)v, (const float *)lse, (const float *)delta, (float *)gk,        \
-                           (float *)gv, p);                                                                                  \
-    } while (0)
-        if (D == 16) { if (drop) MVDETR_ATTN_BWD(16, true); else MVDETR_ATTN_BWD(16, false); }
-        else         { if (drop) MVDETR_ATTN_BWD(32, true); else MVDETR_ATTN_BWD(32, false); }
-#undef MVDETR_ATTN_BWD
-        g_attn_last_kernel = "attn_bwd_mfma";
-    } else {
-        if (D > ATTN_GD) return (int)hipErrorInvalidValue;
-        if (drop) {
-            if (rows)
-                hipLaunchKernelGGL((attn_bwd_dq_generic<T, true>), dim3(attn_rows_grid(rows)), dim3(256), 0, st, go, q, k, v, lse,
-                                   (const T *)delta, gq, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_generic<T, true>), dim3(attn_rows_grid(krows)), dim3(256), 0, st, go, q, k, v, lse,
-                               (const T *)delta, gk, gv, p);
-        } else {
-            if (rows)
-                hipLaunchKernelGGL((attn_bwd_dq_generic<T, false>), dim3(attn_rows_grid(rows)), dim3(256), 0, st, go, q, k, v,
-                                   lse, (const T *)delta, gq, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_generic<T, false>), dim3(attn_rows_grid(krows)), dim3(256), 0, st, go, q, k, v, lse,
-                               (const T *)delta, gk, gv, p);
+    const AttnRoute &r = c.r;
+    const AttnP &p = c.p;
+    const T *go = (const T *)c.go, *q = (const T *)c.q, *k = (const T *)c.k, *v = (const T *)c.v;
+    T *out = (T *)c.out, *lse = (T *)c.lse, *delta = (T *)c.work, *gq = (T *)c.gq, *gk = (T *)c.gk, *gv = (T *)c.gv;
+    const dim3 grid = attn_dim3(r.grid), grid_kv = attn_dim3(r.grid_kv);
+    if (r.with_dq) hipLaunchKernelGGL((attn_delta<T>), dim3(r.grid_delta), dim3(256), 0, c.st, go, out, delta, p);
+    if constexpr (std::is_same<T, float>::value) {
+        if (r.kind == AttnKind::fwd_mfma || r.kind == AttnKind::bwd_mfma) {
+            attn_for_mfma(r, [&](auto d, auto drop) {
+                constexpr int D = decltype(d)::value;
+                constexpr bool DROP = decltype(drop)::value;
+                if (r.kind == AttnKind::fwd_mfma) {
+                    hipLaunchKernelGGL((attn_fwd_mfma<D, DROP>), grid, dim3(512), 0, c.st, q, k, v, out, lse, p);
+                } else {
+                    hipLaunchKernelGGL((attn_bwd_dq_mfma<D, DROP>), grid, dim3(256), 0, c.st, go, q, k, v, lse, delta, gq, p);
+                    hipLaunchKernelGGL((attn_bwd_dkv_mfma<D, DROP>), grid_kv, dim3(256), 0, c.st, go, q, k, v, lse, delta, gk, gv, p);
+                }
+            });
+            return (int)hipGetLastError();
         }
-        g_attn_last_kernel = "attn_bwd_generic";
     }
+    attn_for_drop(r, [&](auto drop) {
+        constexpr bool DROP = decltype(drop)::value;
+        if (r.kind == AttnKind::fwd_generic) {
+            hipLaunchKernelGGL((attn_fwd_generic<T, DROP>), grid, dim3(256), 0, c.st, q, k, v, out, lse, p);
+        } else {
+            if (r.with_dq) hipLaunchKernelGGL((attn_bwd_dq_generic<T, DROP>), grid, dim3(256), 0, c.st, go, q, k, v, lse, delta, gq, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_generic<T, DROP>), grid_kv, dim3(256), 0, c.st, go, q, k, v, lse, delta, gk, gv, p);
+        }
+    });
     return (int)hipGetLastError();
+}
+
+int attn_entry(AttnEntry entry, AttnCall c, const int64_t *strides, int B, int H, int Sq, int Sk, int D, double dropout_p, uint64_t seed)
+{
+    const bool half = entry == AttnEntry::forward_half, bwd = entry == AttnEntry::backward;
+    // the strides of q, k, v, out (and the backward's grad_out, grad_q, grad_k, grad_v): float4 / 16-byte access to every row
+    const int nstr = bwd ? 24 : 12;
+    const bool ptrs16 = aligned(c.q, 16) && aligned(c.k, 16) && aligned(c.v, 16) &&
+                        (bwd ? aligned(c.go, 16) && aligned(c.gq, 16) && aligned(c.gk, 16) && aligned(c.gv, 16) : aligned(c.out, 16));
+    bool strides_ok = strides != nullptr;
+    for (int i = 0; strides && i < nstr; ++i) strides_ok = strides_ok && strides[i] % (half ? 8 : 4) == 0;
+    c.r = attn_route(AttnQuery{entry, half ? 2 : c.type == AttnType::f32 ? 4 : 8, B, H, Sq, Sk, D, dropout_p, half ? g_ah_query_tile.load() : 0,
+                               strides != nullptr, strides_ok, c.q != nullptr, c.k != nullptr, c.v != nullptr, c.out != nullptr,
+                               c.lse != nullptr, c.go != nullptr, c.work != nullptr, c.gq != nullptr, c.gk != nullptr, c.gv != nullptr, ptrs16});
+    const AttnRoute &r = c.r;
+    if (r.status == AttnStatus::empty) return 0;
+    if (r.status != AttnStatus::ok) return (int)(r.status == AttnStatus::invalid_value ? hipErrorInvalidValue : hipErrorNotSupported);
+    c.p.B = B; c.p.H = H; c.p.Sq = Sq; c.p.Sk = Sk; c.p.D = D;
+    int64_t *dst[8] = {c.p.q, c.p.k, c.p.v, c.p.o, c.p.go, c.p.dq, c.p.dk, c.p.dv};
+    for (int i = 0; i < 24; ++i) dst[i / 3][i % 3] = i < nstr ? strides[i] : 0;
+    c.p.thresh = mvdetr_attn_threshold(dropout_p);
+    c.p.seed = seed;
+    c.p.inv_keep = 1.0 / (1.0 - dropout_p);
+    g_attn_last_kernel = r.name;
+    if (half) return attn_launch_forward_half(c);
+    return c.type == AttnType::f32 ? attn_launch<float>(c) : attn_launch<double>(c);
 }
 
 }  // namespace mvdetr
 
+using namespace mvdetr;
+
 extern "C" {
 
-const char *mvdetr_attention_last_kernel(void) { return mvdetr::g_attn_last_kernel.load(); }
+const char *mvdetr_attention_last_kernel(void) { return g_attn_last_kernel.load(); }
 
 int64_t mvdetr_attention_workspace_bytes(int batch, int heads, int sq, int sk, int head_dim, int elem_size)
 {
@@ -783,23 +731,35 @@ int64_t mvdetr_attention_workspace_bytes(int batch, int heads, int sq, int sk, i
     return (int64_t)batch * heads * sq * elem_size;         // delta
 }
 
-#define MVDETR_ATTN_ENTRIES(T, SFX)                                                                                          \
+int mvdetr_attention_route_kind(int entry, int elem_size, int batch, int heads, int sq, int sk, int head_dim, double dropout_p,
+                                int strides_ok, int aligned)
+{
+    if (entry < 0 || entry > (int)AttnEntry::forward_half) return -(int)AttnStatus::invalid_value;
+    const AttnRoute r = attn_route(AttnQuery{(AttnEntry)entry, elem_size, batch, heads, sq, sk, head_dim, dropout_p, g_ah_query_tile.load(), true,
+                                             strides_ok != 0, true, true, true, true, true, true, true, true, true, true, aligned != 0});
+    return r.status == AttnStatus::ok ? (int)r.kind : -(int)r.status;
+}
+
+#define MVDETR_ATTN_ENTRIES(T, SFX, TYPE)                                                                                    \
     int mvdetr_attention_forward_##SFX(void *stream, const T *q, const T *k, const T *v, const int64_t *strides, int batch,  \
                                        int heads, int sq, int sk, int head_dim, double dropout_p, uint64_t seed, T *out,     \
                                        T *lse)                                                                               \
     {                                                                                                                        \
-        return mvdetr::attn_forward<T>(stream, q, k, v, strides, batch, heads, sq, sk, head_dim, dropout_p, seed, out, lse); \
+        return attn_entry(AttnEntry::forward, AttnCall{(hipStream_t)stream, TYPE, nullptr, q, k, v, out, lse, nullptr, nullptr, nullptr, \
+                                                       nullptr, {}, {}}, strides, batch, heads, sq, sk, head_dim, dropout_p, seed);  \
     }                                                                                                                        \
     int mvdetr_attention_backward_##SFX(void *stream, const T *grad_out, const T *q, const T *k, const T *v, const T *out,   \
                                         const T *lse, const int64_t *strides, int batch, int heads, int sq, int sk,          \
                                         int head_dim, double dropout_p, uint64_t seed, void *workspace, T *grad_q,           \
                                         T *grad_k, T *grad_v)                                                                \
     {                                                                                                                        \
-        return mvdetr::attn_backward<T>(stream, grad_out, q, k, v, out, lse, strides, batch, heads, sq, sk, head_dim,        \
-                                        dropout_p, seed, workspace, grad_q, grad_k, grad_v);                                 \
+        /* (the backward only reads out and lse: their const is cast away for the descriptor alone) */                      \
+        return attn_entry(AttnEntry::backward, AttnCall{(hipStream_t)stream, TYPE, grad_out, q, k, v, const_cast<T *>(out),  \
+                                                        const_cast<T *>(lse), workspace, grad_q, grad_k, grad_v, {}, {}},    \
+                          strides, batch, heads, sq, sk, head_dim, dropout_p, seed);                                         \
     }
 
-MVDETR_ATTN_ENTRIES(float, f32)
-MVDETR_ATTN_ENTRIES(double, f64)
+MVDETR_ATTN_ENTRIES(float, f32, AttnType::f32)
+MVDETR_ATTN_ENTRIES(double, f64, AttnType::f64)
 
 }  // extern "C"

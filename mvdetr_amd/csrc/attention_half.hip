@@ -26,73 +26,27 @@
 //                 maximum; query rows >= Sq are clamped for the load and never stored.
 // No scratch, no atomics; every output element is owned by one lane: bit-reproducible run to run.
 #include "../../include/mvdetr_ops.h"
-#include "common.h"
-#include "half_types.h"
-
-#include <atomic>
-#include <type_traits>
+#include "attention.h"
+#include "half_mfma.h"
 
 namespace mvdetr {
-
-extern std::atomic<const char *> g_attn_last_kernel;         // attention.hip
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct AttnHalfP {
     int B, H, Sq, Sk;
     int64_t q[3], k[3], v[3], o[3];                          // element strides: batch, head, token
 };
 
-__device__ __forceinline__ int ah_crow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 __device__ __forceinline__ int ah_tpos(int x) { return 16 * ((x >> 2) & 1) + (x & 3) + 4 * (x >> 3); }
-
-template <typename Conv> __device__ __forceinline__ floatx16 ah_mfma(const uint4 &a, const uint4 &b, const floatx16 &c)
-{
-    if constexpr (std::is_same<Conv, F16>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 constexpr float AH_LOG2E = 1.4426950408889634f;
 constexpr float AH_P_SCALE = 16384.f;                        // 2^14: fp16 probabilities (module comment)
-constexpr float AH_LO_SCALE = 2048.f;                        // 2^11: the fp16 lo term on top of it
-constexpr float AH_HALF_MIN = 6.103515625e-05f;              // 2^-14, the smallest normal half
 
-// two fp32 values -> one word of two 16-bit values, round to nearest even (the lower address first).  bfloat16 takes the
-// hardware's packed conversion (v_cvt_pk_bf16_f32) where BF16::down spends ~6 integer ops per value: the split below converts
-// 32 values per lane and tile, and the probabilities are never NaN.
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-template <typename Conv> __device__ __forceinline__ uint32_t ah_pack2(float a, float b)
-{
-    const floatx2 f = {a, b};
-    if constexpr (std::is_same<Conv, F16>::value)
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, f16x2));
-    else
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2));
-}
-
-// registers 8 s .. 8 s + 7 of p as the hi and lo fragments of k-step s (fp16: p carries AH_P_SCALE, lo AH_LO_SCALE more)
+// registers 8 s .. 8 s + 7 of p as the hi and lo fragments of k-step s (fp16: p carries AH_P_SCALE, lo HALF_LO_SCALE more)
 template <typename Conv> __device__ __forceinline__ void ah_split(const floatx16 &p, int s, uint4 &hi, uint4 &lo)
 {
     uint32_t wh[4], wl[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float x0 = p[8 * s + 2 * j], x1 = p[8 * s + 2 * j + 1], h0, h1;
-        if constexpr (std::is_same<Conv, F16>::value) {
-            wh[j] = ah_pack2<Conv>(x0 < AH_HALF_MIN ? 0.f : x0, x1 < AH_HALF_MIN ? 0.f : x1);   // no subnormal hi: lo takes it whole
-            up2<Conv>(wh[j], h0, h1);
-            wl[j] = ah_pack2<Conv>((x0 - h0) * AH_LO_SCALE, (x1 - h1) * AH_LO_SCALE);
-        } else {
-            wh[j] = ah_pack2<Conv>(x0, x1);
-            up2<Conv>(wh[j], h0, h1);
-            wl[j] = ah_pack2<Conv>(x0 - h0, x1 - h1);
-        }
-    }
+    for (int j = 0; j < 4; ++j) split2<Conv, false>(p[8 * s + 2 * j], p[8 * s + 2 * j + 1], wh[j], wl[j]);
     hi = make_uint4(wh[0], wh[1], wh[2], wh[3]);
     lo = make_uint4(wl[0], wl[1], wl[2], wl[3]);
 }
@@ -180,11 +134,11 @@ __global__ __launch_bounds__(128 * NQW) void attn_fwd_mfma_half(const uint16_t *
             for (int e = 0; e < 16; ++e) s[e] = 0.f;
 #pragma unroll
             for (int c = 0; c < KST; ++c)
-                s = ah_mfma<Conv>(*reinterpret_cast<const uint4 *>(&sK[buf][ks][r][16 * c + 8 * h]), qr[c], s);
+                s = mfma16<Conv>(*reinterpret_cast<const uint4 *>(&sK[buf][ks][r][16 * c + 8 * h]), qr[c], s);
             if (key0 + 32 > p.Sk) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
-                    if (key0 + ah_crow(e, h) >= p.Sk) s[e] = -INFINITY;
+                    if (key0 + mfma_crow(e, h) >= p.Sk) s[e] = -INFINITY;
             }
             float mx = s[0];
 #pragma unroll
@@ -213,11 +167,11 @@ __global__ __launch_bounds__(128 * NQW) void attn_fwd_mfma_half(const uint16_t *
                 const uint4 a = *reinterpret_cast<const uint4 *>(&sVt[buf][ks][r & (D - 1)][16 * h + 8 * c]);
                 uint4 hi, lo;
                 ah_split<Conv>(s, c, hi, lo);
-                o = ah_mfma<Conv>(a, hi, o);
+                o = mfma16<Conv>(a, hi, o);
                 if (FP16)
-                    o2 = ah_mfma<Conv>(a, lo, o2);
+                    o2 = mfma16<Conv>(a, lo, o2);
                 else
-                    o = ah_mfma<Conv>(a, lo, o);
+                    o = mfma16<Conv>(a, lo, o);
             }
         }
         if (kt + 1 < nt) tile.put(sK[buf ^ 1], sVt[buf ^ 1], t);
@@ -225,7 +179,7 @@ __global__ __launch_bounds__(128 * NQW) void attn_fwd_mfma_half(const uint16_t *
     }
     if (FP16) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) o[e] += o2[e] * (1.f / AH_LO_SCALE);
+        for (int e = 0; e < 16; ++e) o[e] += o2[e] * (1.f / HALF_LO_SCALE);
     }
     if (ks == 1) {
 #pragma unroll
@@ -254,66 +208,54 @@ __global__ __launch_bounds__(128 * NQW) void attn_fwd_mfma_half(const uint16_t *
                                                                     down2<Conv>(o[4 * g + 2] * inv_l, o[4 * g + 3] * inv_l));
 }
 
-// queries per workgroup: 128 (NQW = 4) or 64 (NQW = 2).  mvdetr_attn_half_set_query_tile forces one (tests, tools); 0 = by the
-// shape: 128 unless one 64-query workgroup holds every query.  (At 2,700 tokens x 8 heads 128 is the faster of the two although
-// it fills only 176 of 256 compute units: docs/notes/attention_half.md.)
-static std::atomic<int> g_ah_query_tile{0};
+// queries per workgroup: 128 (NQW = 4) or 64 (NQW = 2), four lanes per query.  mvdetr_attn_half_set_query_tile forces one
+// (tests, tools); 0 = by the shape (attn_route).  (At 2,700 tokens x 8 heads 128 is the faster of the two although it fills only
+// 176 of 256 compute units: docs/notes/attention_half.md.)
+std::atomic<int> g_ah_query_tile{0};
 
-static int ah_query_tile(int Sq)
+template <typename Conv> static void attn_launch_half(const AttnCall &c)
 {
-    const int forced = g_ah_query_tile.load();
-    if (forced) return forced;
-    return Sq <= 64 ? 64 : 128;
+    const AttnRoute &r = c.r;
+    AttnHalfP p;
+    p.B = c.p.B; p.H = c.p.H; p.Sq = c.p.Sq; p.Sk = c.p.Sk;
+    for (int j = 0; j < 3; ++j) p.q[j] = c.p.q[j], p.k[j] = c.p.k[j], p.v[j] = c.p.v[j], p.o[j] = c.p.o[j];
+    const dim3 grid(r.grid.x, r.grid.y, r.grid.z);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(4 * r.tile), 0, c.st, (const uint16_t *)c.q, (const uint16_t *)c.k, (const uint16_t *)c.v,
+                           (uint16_t *)c.out, p);
+    };
+    if (r.D == 16) launch(r.tile == 64 ? attn_fwd_mfma_half<Conv, 16, 2> : attn_fwd_mfma_half<Conv, 16, 4>);
+    else launch(r.tile == 64 ? attn_fwd_mfma_half<Conv, 32, 2> : attn_fwd_mfma_half<Conv, 32, 4>);
 }
 
-template <typename Conv>
-static int attn_forward_half(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides, int B, int H,
-                      int Sq, int Sk, int D, uint16_t *out)
+int attn_launch_forward_half(const AttnCall &c)
 {
-    if (!strides || B < 0 || H < 0 || Sq < 0) return (int)hipErrorInvalidValue;
-    if ((D != 16 && D != 32) || Sk < 1 || H > 65535 || B > 65535) return (int)hipErrorNotSupported;
-    for (int i = 0; i < 12; ++i)
-        if (strides[i] % 8 != 0) return (int)hipErrorNotSupported;
-    if ((int64_t)B * H * Sq == 0) return 0;
-    if (!q || !k || !v || !out) return (int)hipErrorInvalidValue;
-    if (!aligned(q, 16) || !aligned(k, 16) || !aligned(v, 16) || !aligned(out, 16)) return (int)hipErrorNotSupported;
-    AttnHalfP p;
-    p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk;
-    int64_t *dst[4] = {p.q, p.k, p.v, p.o};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 3; ++j) dst[i][j] = strides[3 * i + j];
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int tq = ah_query_tile(Sq);
-    const dim3 grid((unsigned)((Sq + tq - 1) / tq), (unsigned)H, (unsigned)B);
-#define MVDETR_ATTN_HALF(DD, NQW) \
-    hipLaunchKernelGGL((attn_fwd_mfma_half<Conv, DD, NQW>), grid, dim3(128 * NQW), 0, st, q, k, v, out, p)
-    if (D == 16) { if (tq == 64) MVDETR_ATTN_HALF(16, 2); else MVDETR_ATTN_HALF(16, 4); }
-    else         { if (tq == 64) MVDETR_ATTN_HALF(32, 2); else MVDETR_ATTN_HALF(32, 4); }
-#undef MVDETR_ATTN_HALF
-    g_attn_last_kernel = "attn_fwd_mfma_half";
+    if (c.type == AttnType::f16) attn_launch_half<F16>(c);
+    else attn_launch_half<BF16>(c);
     return (int)hipGetLastError();
 }
 
 }  // namespace mvdetr
+
+using namespace mvdetr;
 
 extern "C" {
 
 int mvdetr_attn_half_set_query_tile(int queries)
 {
     if (queries != 0 && queries != 64 && queries != 128) return -1;
-    return mvdetr::g_ah_query_tile.exchange(queries);
+    return g_ah_query_tile.exchange(queries);
 }
 
-int mvdetr_attn_forward_f16(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides,
-                            int batch, int heads, int sq, int sk, int head_dim, uint16_t *out)
-{
-    return mvdetr::attn_forward_half<mvdetr::F16>(stream, q, k, v, strides, batch, heads, sq, sk, head_dim, out);
-}
+#define MVDETR_ATTN_HALF_ENTRY(SFX, TYPE)                                                                                    \
+    int mvdetr_attn_forward_##SFX(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides, \
+                                  int batch, int heads, int sq, int sk, int head_dim, uint16_t *out)                         \
+    {                                                                                                                        \
+        return attn_entry(AttnEntry::forward_half, AttnCall{(hipStream_t)stream, TYPE, nullptr, q, k, v, out, nullptr, nullptr, nullptr, \
+                                                            nullptr, nullptr, {}, {}}, strides, batch, heads, sq, sk, head_dim, 0.0, 0); \
+    }
 
-int mvdetr_attn_forward_bf16(void *stream, const uint16_t *q, const uint16_t *k, const uint16_t *v, const int64_t *strides,
-                             int batch, int heads, int sq, int sk, int head_dim, uint16_t *out)
-{
-    return mvdetr::attn_forward_half<mvdetr::BF16>(stream, q, k, v, strides, batch, heads, sq, sk, head_dim, out);
-}
+MVDETR_ATTN_HALF_ENTRY(f16, AttnType::f16)
+MVDETR_ATTN_HALF_ENTRY(bf16, AttnType::bf16)
 
 }  // extern "C"

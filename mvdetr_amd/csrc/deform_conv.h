@@ -1,17 +1,33 @@
 // What the deformable-convolution kernels of deform_conv.hip (fp32 / fp64) and deform_conv_half.hip (float16 / bfloat16)
-// share: the call's shape, the bilinear footprint of one tap, the pixel decomposition and the MFMA tile geometry.
+// share: the bilinear footprint of one tap, the pixel decomposition, and one call as the C ABI entries of deform_conv.hip fill
+// it.  What a call may ask for is checked by dc_route() (deform_conv_route.h: the shape and the tile constants too), once,
+// before a launcher runs; a launcher picks the instantiation and launches.
 #pragma once
 #include "common.h"
-
-#include <atomic>
+#include "deform_conv_route.h"
 
 namespace mvdetr {
 
-extern std::atomic<const char *> g_dc_last_kernel;         // deform_conv.hip
+enum class DcType { f16, bf16, f32, f64 };
 
-struct DcShape {
-    int B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G;
+struct DcCall {
+    hipStream_t st;
+    DcType type;
+    const void *gout, *in, *off, *wt, *bias;        // gout: the backward's grad_out
+    void *out, *gin, *goff, *gw;
+    int nhwc, relu;
+    int64_t obs;                                    // the 16-bit entry's out_batch_stride
+    DcRoute r;                                      // r.s: the shape
 };
+
+// the one entry path (deform_conv.hip) and the C ABI's shape arguments as it takes them
+#define MVDETR_DC_SHAPE_PARAMS                                                                                                   \
+    int batch, int in_channels, int in_h, int in_w, int out_channels, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, \
+        int pad_w, int dil_h, int dil_w, int offset_groups
+#define MVDETR_DC_SHAPE {batch, in_channels, in_h, in_w, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_groups}
+int dc_entry(DcEntry entry, DcCall c, const int (&sh)[14]);
+// dc_fwd_mfma_half (deform_conv_half.hip)
+int dc_launch_forward_half(const DcCall &c);
 
 // bilinear footprint of one tap: corner pixel indices (y * W + x), weights, validity; `in` = the sample is not 0
 template <typename T> struct DcFoot {
@@ -46,9 +62,6 @@ template <typename T> __device__ __forceinline__ DcFoot<T> dc_foot(T y, T x, int
     return f;
 }
 
-constexpr int DC_TP = 64;       // output pixels per forward / g_col workgroup
-constexpr int DC_TO = 128;      // output (forward) or input (g_col) channels per workgroup: 4 waves x 32 rows
-
 __device__ __forceinline__ void dc_pixel(const DcShape &s, int64_t gp, int &b, int &p, int &ho, int &wo)
 {
     const int HWo = s.Ho * s.Wo;
@@ -56,21 +69,6 @@ __device__ __forceinline__ void dc_pixel(const DcShape &s, int64_t gp, int &b, i
     p = (int)(gp - (int64_t)b * HWo);
     ho = p / s.Wo;
     wo = p - ho * s.Wo;
-}
-
-inline bool dc_shape(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G,
-                     DcShape &s)
-{
-    if (B < 0 || C < 0 || H < 1 || W < 1 || Co < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
-        dw < 1 || G < 1 || C % G != 0)
-        return false;
-    const int Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1, Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (H + 2 * ph - dh * (kh - 1) - 1 < 0 || W + 2 * pw - dw * (kw - 1) - 1 < 0) return false;
-    if ((int64_t)B * C * H * W >= (1ll << 31) || (int64_t)B * Co * Ho * Wo >= (1ll << 31) ||
-        (int64_t)B * 2 * G * kh * kw * Ho * Wo >= (1ll << 31))
-        return false;
-    s = DcShape{B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G};
-    return true;
 }
 
 }  // namespace mvdetr

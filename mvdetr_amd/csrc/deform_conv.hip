@@ -26,16 +26,11 @@
 #include "../../include/mvdetr_ops.h"
 #include "common.h"
 #include "deform_conv.h"
+#include "half_mfma.h"
 
-#include <algorithm>
 #include <atomic>
-#include <type_traits>
 
 namespace mvdetr {
-
-std::atomic<const char *> g_dc_last_kernel{"none"};        // (deform_conv_half.hip sets it too)
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // sampling position of output pixel (ho, wo), tap (i, j), from the offset tensor [B, 2 * G * T, Ho, Wo]
 template <typename T>
@@ -269,7 +264,7 @@ __global__ __launch_bounds__(256) void dc_fwd_mfma(const float *__restrict__ in,
         }
     }
     if (!active) return;
-    // D[i][j]: column j = lane & 31 (pixel), row i = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (output channel)
+    // D[i][j]: column j = lane & 31 (pixel), row i = mfma_crow(reg, lane >> 5) (output channel)
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int64_t q = p0 + n * 32 + r;
@@ -279,7 +274,7 @@ __global__ __launch_bounds__(256) void dc_fwd_mfma(const float *__restrict__ in,
         float *ob = out + (int64_t)qb * s.Co * HWo + qp;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int o = o0 + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int o = o0 + wave * 32 + mfma_crow(e, h);
             ob[(int64_t)o * HWo] = acc[n][e] + (bias ? bias[o] : 0.f);
         }
     }
@@ -392,7 +387,6 @@ __global__ __launch_bounds__(256) void dc_bwd_col_mfma(const float *__restrict__
 
 // grad_W[o, c, tap] (+)= sum over a pixel range of grad_out[o, p] x col[(c, tap), p]: workgroup = (tap, 32 input channels)
 // x 128 output channels x one pixel range; K loop over 32-pixel chunks, both tiles staged in LDS
-constexpr int DC_WP = 32;
 __global__ __launch_bounds__(256) void dc_bwd_weight_mfma(const float *__restrict__ gout, const float *__restrict__ in,
                                                           const float *__restrict__ off, float *__restrict__ gw, DcShape s,
                                                           int64_t pix_per_split)
@@ -460,122 +454,116 @@ __global__ __launch_bounds__(256) void dc_bwd_weight_mfma(const float *__restric
     if (c >= s.C) return;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int o = o0 + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int o = o0 + wave * 32 + mfma_crow(e, h);
         float *dst = gw + ((int64_t)o * s.C + c) * T_ + tap;
         if (gridDim.z == 1) *dst = acc[e];
         else atomicAdd(dst, acc[e]);                                   // (zeroed by the entry)
     }
 }
 
-// ---- entries -----------------------------------------------------------------------------------------------------------
+// ---- launchers and the entry path: one DcCall, dc_route(), a switch on the route's kind --------------------------------------
 
-template <typename T> static bool dc_fast(const DcShape &s, int nhwc, const T *in)
+static std::atomic<const char *> g_dc_last_kernel{"none"};
+
+static dim3 dc_dim3(const DcGrid &g) { return dim3(g.x, g.y, g.z); }
+static size_t dc_elem_size(DcType type) { return type == DcType::f64 ? 8 : type == DcType::f32 ? 4 : 2; }
+
+// zeroes grad_weight or grad_offset
+static hipError_t dc_zero(const DcCall &c, bool weight)
 {
-    if constexpr (!std::is_same<T, float>::value) return false;
-    return nhwc && s.G == 1 && s.C % 16 == 0 && s.C > 0 && s.Co % 32 == 0 && s.Co > 0 && aligned(in, 16);
+    const DcShape &s = c.r.s;
+    const size_t n = weight ? (size_t)s.Co * s.C : (size_t)s.B * s.Ho * s.Wo * 2 * s.G;
+    return hipMemsetAsync(weight ? c.gw : c.goff, 0, dc_elem_size(c.type) * n * s.kh * s.kw, c.st);
 }
 
-static unsigned dc_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
-
-template <typename T>
-static int dc_forward(void *stream, const T *in, const T *off, const T *wt, const T *bias, int B, int C, int H, int W, int Co,
-                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, int nhwc, T *out)
+template <typename T> static int dc_launch_generic(const DcCall &c)
 {
-    DcShape s;
-    if (!dc_shape(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, G, s)) return (int)hipErrorInvalidValue;
-    const int64_t P = (int64_t)B * s.Ho * s.Wo;
-    if (P * Co == 0) return 0;
-    if (!out || !off || (C > 0 && (!in || !wt))) return (int)hipErrorInvalidValue;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dc_fast(s, nhwc, in)) {
-        const dim3 grid((unsigned)((P + DC_TP - 1) / DC_TP), (unsigned)((Co + DC_TO - 1) / DC_TO));
-        if (C % 32 == 0)
-            hipLaunchKernelGGL((dc_fwd_mfma<32>), grid, dim3(256), 0, st, (const float *)in, (const float *)off,
-                               (const float *)wt, (const float *)bias, (float *)out, s);
-        else
-            hipLaunchKernelGGL((dc_fwd_mfma<16>), grid, dim3(256), 0, st, (const float *)in, (const float *)off,
-                               (const float *)wt, (const float *)bias, (float *)out, s);
-        g_dc_last_kernel = "dc_fwd_mfma";
+    const DcRoute &r = c.r;
+    const T *in = (const T *)c.in, *off = (const T *)c.off, *wt = (const T *)c.wt, *gout = (const T *)c.gout;
+    const int cl = c.nhwc ? 1 : 0;
+    if (r.kind == DcKind::fwd_generic) {
+        hipLaunchKernelGGL((dc_fwd_generic<T>), dc_dim3(r.grid[0]), dim3(256), 0, c.st, in, off, wt, (const T *)c.bias, (T *)c.out, r.s, cl);
     } else {
-        hipLaunchKernelGGL((dc_fwd_generic<T>), dim3(dc_grid(P * Co)), dim3(256), 0, st, in, off, wt, bias, out, s, nhwc ? 1 : 0);
-        g_dc_last_kernel = "dc_fwd_generic";
+        hipLaunchKernelGGL((dc_bwd_input_generic<T>), dc_dim3(r.grid[0]), dim3(256), 0, c.st, gout, in, off, wt, (T *)c.gin, (T *)c.goff, r.s, cl);
+        hipLaunchKernelGGL((dc_bwd_weight_generic<T>), dc_dim3(r.grid[1]), dim3(256), 0, c.st, gout, in, off, (T *)c.gw, r.s, cl);
     }
     return (int)hipGetLastError();
 }
 
-template <typename T>
-static int dc_backward(void *stream, const T *gout, const T *in, const T *off, const T *wt, int B, int C, int H, int W, int Co,
-                       int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, int nhwc, T *gin, T *goff, T *gw)
+static int dc_launch_mfma(const DcCall &c)
 {
-    DcShape s;
-    if (!dc_shape(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, G, s)) return (int)hipErrorInvalidValue;
-    const int T_ = kh * kw;
-    const int64_t P = (int64_t)B * s.Ho * s.Wo, nw = (int64_t)Co * C * T_;
-    if ((P * Co * C != 0 && (!gout || !in || !off || !wt || !gin)) || (P && !goff) || (nw && !gw))
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    if (P == 0 || Co == 0 || C == 0) {                  // nothing flows: the written outputs are zero
-        if (P && goff) e = hipMemsetAsync(goff, 0, sizeof(T) * P * 2 * G * T_, st);
-        if (e == hipSuccess && nw) e = hipMemsetAsync(gw, 0, sizeof(T) * nw, st);
+    const DcRoute &r = c.r;
+    const float *in = (const float *)c.in, *off = (const float *)c.off, *wt = (const float *)c.wt, *gout = (const float *)c.gout;
+    if (r.kind == DcKind::fwd_mfma) {
+        hipLaunchKernelGGL(r.KC == 32 ? dc_fwd_mfma<32> : dc_fwd_mfma<16>, dc_dim3(r.grid[0]), dim3(256), 0, c.st, in, off, wt,
+                           (const float *)c.bias, (float *)c.out, r.s);
+        return (int)hipGetLastError();
+    }
+    hipError_t e;
+    if (r.zero_goff && (e = dc_zero(c, false)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dc_bwd_col_mfma, dc_dim3(r.grid[0]), dim3(256), 0, c.st, gout, in, off, wt, (float *)c.gin, (float *)c.goff, r.s);
+    if (r.zero_gw && (e = dc_zero(c, true)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dc_bwd_weight_mfma, dc_dim3(r.grid[1]), dim3(256), 0, c.st, gout, in, off, (float *)c.gw, r.s, r.pps);
+    return (int)hipGetLastError();
+}
+
+int dc_entry(DcEntry entry, DcCall c, const int (&sh)[14])
+{
+    // (the last flag is the 16-bit entry's alone; a null bias counts as aligned, and the other entries' null `out` too)
+    c.r = dc_route(DcQuery{entry, (int)dc_elem_size(c.type), sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], sh[6], sh[7], sh[8], sh[9], sh[10],
+                           sh[11], sh[12], sh[13], c.nhwc, c.obs, c.in != nullptr, c.off != nullptr, c.wt != nullptr, c.out != nullptr,
+                           c.gout != nullptr, c.gin != nullptr, c.goff != nullptr, c.gw != nullptr, aligned(c.in, 16), aligned(c.wt, 16),
+                           aligned(c.off, 2) && aligned(c.out, 2) && aligned(c.bias, 2)});
+    const DcRoute &r = c.r;
+    if (r.status == DcStatus::empty) return 0;
+    if (r.status != DcStatus::ok) return (int)(r.status == DcStatus::invalid_value ? hipErrorInvalidValue : hipErrorNotSupported);
+    if (r.name) g_dc_last_kernel = r.name;
+    switch (r.kind) {
+    case DcKind::bwd_zero_fill: {                       // nothing flows: the written outputs are zero
+        hipError_t e = r.zero_goff ? dc_zero(c, false) : hipSuccess;
+        if (e == hipSuccess && r.zero_gw) e = dc_zero(c, true);
         return (int)e;
     }
-    if (dc_fast(s, nhwc, in)) {
-        const unsigned cblocks = (unsigned)((C + DC_TO - 1) / DC_TO);
-        if (cblocks > 1) e = hipMemsetAsync(goff, 0, sizeof(T) * P * 2 * T_, st);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dc_bwd_col_mfma, dim3((unsigned)((P + DC_TP - 1) / DC_TP), cblocks, (unsigned)T_), dim3(256), 0, st,
-                           (const float *)gout, (const float *)in, (const float *)off, (const float *)wt, (float *)gin,
-                           (float *)goff, s);
-        // pixel ranges: enough workgroups to fill the chip (~2048), each range a multiple of the 32-pixel chunk
-        const int64_t kblocks = (int64_t)T_ * ((C + 31) / 32) * ((Co + DC_TO - 1) / DC_TO);
-        const int64_t chunks = (P + DC_WP - 1) / DC_WP;
-        const int64_t splits = std::max<int64_t>(1, std::min<int64_t>(chunks, (2048 + kblocks - 1) / kblocks));
-        const int64_t pps = ((chunks + splits - 1) / splits) * DC_WP;
-        const unsigned nz = (unsigned)((P + pps - 1) / pps);
-        if (nz > 1) e = hipMemsetAsync(gw, 0, sizeof(T) * nw, st);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dc_bwd_weight_mfma, dim3((unsigned)(T_ * ((C + 31) / 32)), (unsigned)((Co + DC_TO - 1) / DC_TO), nz),
-                           dim3(256), 0, st, (const float *)gout, (const float *)in, (const float *)off, (float *)gw, s, pps);
-        g_dc_last_kernel = "dc_bwd_mfma";
-    } else {
-        hipLaunchKernelGGL((dc_bwd_input_generic<T>), dim3(dc_grid(P * G * T_)), dim3(256), 0, st, gout, in, off, wt, gin, goff,
-                           s, nhwc ? 1 : 0);
-        hipLaunchKernelGGL((dc_bwd_weight_generic<T>), dim3((unsigned)(C * T_), (unsigned)((Co + 255) / 256)), dim3(256), 0, st,
-                           gout, in, off, gw, s, nhwc ? 1 : 0);
-        g_dc_last_kernel = "dc_bwd_generic";
+    case DcKind::fwd_mfma_half: return dc_launch_forward_half(c);
+    case DcKind::fwd_mfma:
+    case DcKind::bwd_mfma: return dc_launch_mfma(c);
+    default: return c.type == DcType::f32 ? dc_launch_generic<float>(c) : dc_launch_generic<double>(c);
     }
-    return (int)hipGetLastError();
 }
 
 }  // namespace mvdetr
 
+using namespace mvdetr;
+
 extern "C" {
 
-const char *mvdetr_deform_conv2d_last_kernel(void) { return mvdetr::g_dc_last_kernel.load(); }
+const char *mvdetr_deform_conv2d_last_kernel(void) { return g_dc_last_kernel.load(); }
 
-#define MVDETR_DC_ENTRIES(T, SFX)                                                                                            \
+int mvdetr_deform_conv2d_route_kind(int entry, int elem_size, MVDETR_DC_SHAPE_PARAMS, int input_nhwc, int aligned)
+{
+    if (entry < 0 || entry > (int)DcEntry::forward_half) return -(int)DcStatus::invalid_value;
+    const int sh[14] = MVDETR_DC_SHAPE;
+    const DcRoute r = dc_route(DcQuery{(DcEntry)entry, elem_size, sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], sh[6], sh[7], sh[8], sh[9],
+                                       sh[10], sh[11], sh[12], sh[13], input_nhwc, INT64_MAX, true, true, true, true, true, true, true, true,
+                                       aligned != 0, aligned != 0, true});
+    return r.status == DcStatus::ok ? (int)r.kind : -(int)r.status;
+}
+
+#define MVDETR_DC_ENTRIES(T, SFX, TYPE)                                                                                      \
     int mvdetr_deform_conv2d_forward_##SFX(void *stream, const T *input, const T *offset, const T *weight, const T *bias,   \
-                                           int batch, int in_channels, int in_h, int in_w, int out_channels, int kernel_h,   \
-                                           int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,        \
-                                           int dil_w, int offset_groups, int input_nhwc, T *out)                             \
+                                           MVDETR_DC_SHAPE_PARAMS, int input_nhwc, T *out)                                   \
     {                                                                                                                        \
-        return mvdetr::dc_forward<T>(stream, input, offset, weight, bias, batch, in_channels, in_h, in_w, out_channels,      \
-                                     kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_groups,      \
-                                     input_nhwc, out);                                                                       \
+        return dc_entry(DcEntry::forward, DcCall{(hipStream_t)stream, TYPE, nullptr, input, offset, weight, bias, out, nullptr, nullptr, \
+                                                 nullptr, input_nhwc, 0, 0, {}}, MVDETR_DC_SHAPE);                           \
     }                                                                                                                        \
-    int mvdetr_deform_conv2d_backward_##SFX(void *stream, const T *grad_out, const T *input, const T *offset,               \
-                                            const T *weight, int batch, int in_channels, int in_h, int in_w,                 \
-                                            int out_channels, int kernel_h, int kernel_w, int stride_h, int stride_w,        \
-                                            int pad_h, int pad_w, int dil_h, int dil_w, int offset_groups, int input_nhwc,   \
-                                            T *grad_input, T *grad_offset, T *grad_weight)                                   \
+    int mvdetr_deform_conv2d_backward_##SFX(void *stream, const T *grad_out, const T *input, const T *offset, const T *weight,   \
+                                            MVDETR_DC_SHAPE_PARAMS, int input_nhwc, T *grad_input, T *grad_offset, T *grad_weight) \
     {                                                                                                                        \
-        return mvdetr::dc_backward<T>(stream, grad_out, input, offset, weight, batch, in_channels, in_h, in_w,               \
-                                      out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,      \
-                                      offset_groups, input_nhwc, grad_input, grad_offset, grad_weight);                      \
+        return dc_entry(DcEntry::backward, DcCall{(hipStream_t)stream, TYPE, grad_out, input, offset, weight, nullptr, nullptr,  \
+                                                  grad_input, grad_offset, grad_weight, input_nhwc, 0, 0, {}}, MVDETR_DC_SHAPE); \
     }
 
-MVDETR_DC_ENTRIES(float, f32)
-MVDETR_DC_ENTRIES(double, f64)
+MVDETR_DC_ENTRIES(float, f32, DcType::f32)
+MVDETR_DC_ENTRIES(double, f64, DcType::f64)
 
 }  // extern "C"

@@ -26,59 +26,16 @@
 #include "../../include/mvdetr_ops.h"
 #include "common.h"
 #include "deform_conv.h"
-#include "half_types.h"
-
-#include <type_traits>
+#include "half_mfma.h"
 
 namespace mvdetr {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-constexpr float DCH_LO_SCALE = 2048.f;                       // 2^11: the fp16 lo term (module comment)
-constexpr float DCH_HALF_MIN = 6.103515625e-05f;             // 2^-14, the smallest normal half
-
-template <typename Conv> __device__ __forceinline__ floatx16 dch_mfma(const uint4 &a, const uint4 &b, const floatx16 &c)
-{
-    if constexpr (std::is_same<Conv, F16>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// two fp32 values -> one word of two 16-bit values, round to nearest even (the lower address first): the hardware's packed
-// conversions.  The column values are never NaN unless the input is.
-template <typename Conv> __device__ __forceinline__ uint32_t dch_pack2(float a, float b)
-{
-    const floatx2 f = {a, b};
-    if constexpr (std::is_same<Conv, F16>::value)
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, f16x2));
-    else
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2));
-}
-
-// eight fp32 column values -> the hi and lo images (fp16: lo carries DCH_LO_SCALE)
+// eight fp32 column values -> the hi and lo images (fp16: lo carries HALF_LO_SCALE)
 template <typename Conv> __device__ __forceinline__ void dch_split(const float (&x)[8], uint4 &hi, uint4 &lo)
 {
     uint32_t wh[4], wl[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float x0 = x[2 * j], x1 = x[2 * j + 1];
-        float h0, h1;
-        if constexpr (std::is_same<Conv, F16>::value) {
-            wh[j] = dch_pack2<Conv>(fabsf(x0) < DCH_HALF_MIN ? 0.f : x0, fabsf(x1) < DCH_HALF_MIN ? 0.f : x1);
-            up2<Conv>(wh[j], h0, h1);
-            wl[j] = dch_pack2<Conv>((x0 - h0) * DCH_LO_SCALE, (x1 - h1) * DCH_LO_SCALE);
-        } else {
-            wh[j] = dch_pack2<Conv>(x0, x1);
-            up2<Conv>(wh[j], h0, h1);
-            wl[j] = dch_pack2<Conv>(x0 - h0, x1 - h1);
-        }
-    }
+    for (int j = 0; j < 4; ++j) split2<Conv, true>(x[2 * j], x[2 * j + 1], wh[j], wl[j]);
     hi = make_uint4(wh[0], wh[1], wh[2], wh[3]);
     lo = make_uint4(wl[0], wl[1], wl[2], wl[3]);
 }
@@ -187,17 +144,17 @@ __global__ __launch_bounds__(256) void dc_fwd_mfma_half(const uint16_t *__restri
                 for (int n = 0; n < 2; ++n) {
                     const uint4 bh = *reinterpret_cast<const uint4 *>(&sXh[buf][n * 32 + r][16 * ks + 8 * h]);
                     const uint4 bl = *reinterpret_cast<const uint4 *>(&sXl[buf][n * 32 + r][16 * ks + 8 * h]);
-                    acc[n] = dch_mfma<Conv>(a, bh, acc[n]);
+                    acc[n] = mfma16<Conv>(a, bh, acc[n]);
                     if (FP16)
-                        acc2[n] = dch_mfma<Conv>(a, bl, acc2[n]);
+                        acc2[n] = mfma16<Conv>(a, bl, acc2[n]);
                     else
-                        acc[n] = dch_mfma<Conv>(a, bl, acc[n]);
+                        acc[n] = mfma16<Conv>(a, bl, acc[n]);
                 }
             }
         }
     }
     if (!active) return;
-    // D[i][j]: column j = lane & 31 (pixel), row i = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (output channel)
+    // D[i][j]: column j = lane & 31 (pixel), row i = mfma_crow(reg, lane >> 5) (output channel)
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int64_t q = p0 + n * 32 + r;
@@ -207,9 +164,9 @@ __global__ __launch_bounds__(256) void dc_fwd_mfma_half(const uint16_t *__restri
         uint16_t *ob = out + (int64_t)qb * obs + qp;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int o = o0 + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int o = o0 + wave * 32 + mfma_crow(e, h);
             float v = acc[n][e];
-            if (FP16) v += acc2[n][e] * (1.f / DCH_LO_SCALE);
+            if (FP16) v += acc2[n][e] * (1.f / HALF_LO_SCALE);
             if (bias) v += Conv::up(bias[o]);
             if (relu) v = fmaxf(v, 0.f);
             ob[(int64_t)o * HWo] = Conv::down(v);
@@ -217,55 +174,37 @@ __global__ __launch_bounds__(256) void dc_fwd_mfma_half(const uint16_t *__restri
     }
 }
 
-template <typename Conv>
-static int dc_forward_half(void *stream, const uint16_t *in, const uint16_t *off, const uint16_t *wt, const uint16_t *bias, int B,
-                           int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G,
-                           int nhwc, int relu, int64_t obs, uint16_t *out)
+template <typename Conv> static void dc_launch_half(const DcCall &c)
 {
-    DcShape s;
-    if (!dc_shape(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, G, s)) return (int)hipErrorInvalidValue;
-    if (!in || !off || !wt || !out) return (int)hipErrorInvalidValue;
-    if (G != 1 || !nhwc || C < 16 || C % 16 != 0 || Co < 32 || Co % 32 != 0) return (int)hipErrorNotSupported;
-    if (!aligned(in, 16) || !aligned(wt, 16) || !aligned(off, 2) || !aligned(out, 2) || (bias && !aligned(bias, 2)))
-        return (int)hipErrorNotSupported;
-    const int64_t HWo = (int64_t)s.Ho * s.Wo, P = (int64_t)B * HWo;
-    if (obs < (int64_t)Co * HWo || (int64_t)kh * kw * Co * C >= (1ll << 31))
-        return (int)hipErrorInvalidValue;
-    if (P == 0) return 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((P + DC_TP - 1) / DC_TP), (unsigned)((Co + DC_TO - 1) / DC_TO));
-    if (C % 32 == 0)
-        hipLaunchKernelGGL((dc_fwd_mfma_half<Conv, 32>), grid, dim3(256), 0, st, in, off, wt, bias, out, s, relu, obs);
-    else
-        hipLaunchKernelGGL((dc_fwd_mfma_half<Conv, 16>), grid, dim3(256), 0, st, in, off, wt, bias, out, s, relu, obs);
-    g_dc_last_kernel = "dc_fwd_mfma_half";
+    const DcRoute &r = c.r;
+    hipLaunchKernelGGL((r.KC == 32 ? dc_fwd_mfma_half<Conv, 32> : dc_fwd_mfma_half<Conv, 16>), dim3(r.grid[0].x, r.grid[0].y), dim3(256), 0, c.st,
+                       (const uint16_t *)c.in, (const uint16_t *)c.off, (const uint16_t *)c.wt, (const uint16_t *)c.bias, (uint16_t *)c.out,
+                       r.s, c.relu, c.obs);
+}
+
+int dc_launch_forward_half(const DcCall &c)
+{
+    if (c.type == DcType::f16) dc_launch_half<F16>(c);
+    else dc_launch_half<BF16>(c);
     return (int)hipGetLastError();
 }
 
 }  // namespace mvdetr
 
+using namespace mvdetr;
+
 extern "C" {
 
-int mvdetr_deform_conv2d_forward_f16(void *stream, const uint16_t *input, const uint16_t *offset, const uint16_t *weight,
-                                     const uint16_t *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
-                                     int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
-                                     int dil_w, int offset_groups, int input_nhwc, int relu, int64_t out_batch_stride,
-                                     uint16_t *out)
-{
-    return mvdetr::dc_forward_half<mvdetr::F16>(stream, input, offset, weight, bias, batch, in_channels, in_h, in_w, out_channels,
-                                                kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_groups,
-                                                input_nhwc, relu, out_batch_stride, out);
-}
+#define MVDETR_DC_HALF_ENTRY(SFX, TYPE)                                                                                      \
+    int mvdetr_deform_conv2d_forward_##SFX(void *stream, const uint16_t *input, const uint16_t *offset, const uint16_t *weight,  \
+                                           const uint16_t *bias, MVDETR_DC_SHAPE_PARAMS, int input_nhwc, int relu,           \
+                                           int64_t out_batch_stride, uint16_t *out)                                          \
+    {                                                                                                                        \
+        return dc_entry(DcEntry::forward_half, DcCall{(hipStream_t)stream, TYPE, nullptr, input, offset, weight, bias, out, nullptr, \
+                                                      nullptr, nullptr, input_nhwc, relu, out_batch_stride, {}}, MVDETR_DC_SHAPE);   \
+    }
 
-int mvdetr_deform_conv2d_forward_bf16(void *stream, const uint16_t *input, const uint16_t *offset, const uint16_t *weight,
-                                      const uint16_t *bias, int batch, int in_channels, int in_h, int in_w, int out_channels,
-                                      int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
-                                      int dil_w, int offset_groups, int input_nhwc, int relu, int64_t out_batch_stride,
-                                      uint16_t *out)
-{
-    return mvdetr::dc_forward_half<mvdetr::BF16>(stream, input, offset, weight, bias, batch, in_channels, in_h, in_w,
-                                                 out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
-                                                 offset_groups, input_nhwc, relu, out_batch_stride, out);
-}
+MVDETR_DC_HALF_ENTRY(f16, DcType::f16)
+MVDETR_DC_HALF_ENTRY(bf16, DcType::bf16)
 
 }  // extern "C"

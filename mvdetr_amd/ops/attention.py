@@ -9,9 +9,9 @@ probabilities from the saved log-sum-exp, uses no atomics and is bit-reproducibl
 
 16-bit inference: CUDA float16 / bfloat16 q, k, v with ``dropout_p == 0`` and nothing to differentiate run
 ``attn_fwd_mfma_half`` (csrc/attention_half.hip: 16-bit MFMA, fp32 softmax, the probabilities as two 16-bit terms, one
-rounding on the way out) when the head dimension is 16 or 32 and every row starts 16-byte aligned; every other such call
-is ``attention(q.float(), k.float(), v.float()).to(dtype)`` on the fp32 kernels.  A 16-bit call that needs gradients or
-dropout is refused, and there is no 16-bit host path.
+rounding on the way out) where the library's route (csrc/attention_route.h) takes the call; every other such call is
+``attention(q.float(), k.float(), v.float()).to(dtype)`` on the fp32 kernels.  A 16-bit call that needs gradients or dropout is
+refused, and there is no 16-bit host path.
 
 * ``attention(q, k, v, dropout_p=0.0, seed=None)``: q [B, H, Sq, D], k and v [B, H, Sk, D] -> [B, H, Sq, D].  The operands
   may be any views whose last dimension is contiguous (a head-split view of a seq-first or batch-first projection is read in
@@ -138,17 +138,16 @@ def _half_rows_ok(t) -> bool:
 def _attention_half(q, k, v):
     """The 16-bit forward (inference only; the caller has checked dtype, device, dropout and grad)."""
     B, H, Sq, D = q.shape
-    if D in (16, 32) and B <= 65535 and H <= 65535 and all(_half_rows_ok(t) for t in (q, k, v)):
-        out = _empty_like_order(q)
-        if out.numel() and _half_rows_ok(out):
+    if all(_half_rows_ok(t) for t in (q, k, v)):                # (about the tensors; everything else is the route's)
+        ok = int(_half_rows_ok(out := _empty_like_order(q)))
+        if _lib.attn_route(_lib.ROUTE_FORWARD_HALF, 2, B, H, Sq, k.shape[2], D, 0.0, ok, ok) == "fwd_mfma_half":
             with torch.cuda.device(q.device):
                 rc = getattr(_lib.lib(), f"mvdetr_attn_forward_{_lib.suffix(q.dtype, half_ok=True)}")(
                     _lib.current_stream_ptr(q.device), q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v, out),
                     B, H, Sq, k.shape[2], D, out.data_ptr())
             _lib.check(rc, "attention_forward_half")
             return out
-    # what the 16-bit kernel does not take (another head dimension, rows off alignment): the fp32 kernels on the upcast
-    return attention(q.float(), k.float(), v.float()).to(q.dtype)
+    return attention(q.float(), k.float(), v.float()).to(q.dtype)       # what the 16-bit kernel does not take
 
 
 def attention(q, k, v, dropout_p=0.0, seed=None):

@@ -8,16 +8,15 @@ The reference's ``deform_conv`` ground-plane aggregator (multiview_detector/mode
 
 Sampling: tap (i, j) of output pixel (h, w) reads the input bilinearly at y = h * stride - padding + i * dilation + dy
 (x likewise) in pixel units, 0 outside (-1, H) x (-1, W); offset channel 2 (g * kh * kw + i * kw + j) is dy of offset group
-g, the next one dx (include/mvdetr_ops.h).  CUDA tensors run the HIP kernels of csrc/deform_conv.hip -- fp32 with a
-channel-last input (``torch.channels_last``, e.g. ``warp_perspective(..., channels_last_out=True)`` viewed as NCHW), one
-offset group, C_in % 16 == 0 and C_out % 32 == 0 take the MFMA implicit GEMM; an NCHW input of that shape is transposed to
-channel-last first; everything else takes the generic kernels.  CPU tensors run the library's host path.  Gradients flow to
-input, offset, weight and bias; the backward is not bit-reproducible run to run (atomics), like torchvision's CUDA kernel.
+g, the next one dx (include/mvdetr_ops.h).  CUDA tensors run the HIP kernels of csrc/deform_conv.hip; which one is the
+library's decision (csrc/deform_conv_route.h): fp32 with a channel-last input (``torch.channels_last``, e.g.
+``warp_perspective(..., channels_last_out=True)`` viewed as NCHW) of the MFMA shape takes the MFMA implicit GEMM, an NCHW input
+of that shape is transposed to channel-last first, everything else the generic kernels.  CPU tensors run the library's host path.
+Gradients flow to input, offset, weight and bias; the backward is not bit-reproducible (atomics), like torchvision's CUDA kernel.
 
-16-bit inference (float16 / bfloat16 CUDA tensors of one dtype, forward only): a call of the MFMA shape (one offset group,
-C_in % 16 == 0, C_out % 32 == 0) runs ``dc_fwd_mfma_half`` of csrc/deform_conv_half.hip -- 16-bit storage, fp32 arithmetic,
-one rounding on the way out -- on a channel-last input read in place (an NCHW input is copied to channel-last first); the
-kernel takes the weight permuted to [kh * kw, C_out, C_in], one small copy per call that ``DeformConv2d`` caches in eval mode.
+16-bit inference (float16 / bfloat16 CUDA tensors of one dtype, forward only): a call of the 16-bit MFMA shape runs
+``dc_fwd_mfma_half`` of csrc/deform_conv_half.hip -- 16-bit storage, fp32 arithmetic, one rounding on the way out -- on a
+channel-last input read in place (an NCHW input is copied to channel-last first); the kernel takes the weight permuted to [kh * kw, C_out, C_in], one small copy per call that ``DeformConv2d`` caches in eval mode.
 Every other 16-bit CUDA call (odd channel counts, two offset groups, a data pointer that is not 16-byte aligned) is computed
 as ``deform_conv2d(x.float(), ...).to(dtype)`` on the fp32 routes above, and ``MVDETR_DEFORM_CONV_HALF=0`` (read per call)
 sends the kernel's calls there too.  A 16-bit call with a tensor that requires grad while grad is enabled raises: forward only.
@@ -45,18 +44,15 @@ def last_kernel() -> str:
     return _lib.lib().mvdetr_deform_conv2d_last_kernel().decode()
 
 
-def _fast_shape(x, weight, offset_groups):
-    B, C, H, W = x.shape
-    return (x.is_cuda and x.dtype == torch.float32 and offset_groups == 1 and C % 16 == 0 and C > 0
-            and weight.shape[0] % 32 == 0 and weight.shape[0] > 0 and B <= 65535 and (H * W + 63) // 64 <= 65535)
-
-
-def _layout(x, weight, offset_groups):
-    """(tensor whose memory the kernels read, nhwc flag): a channel-last input is read in place; an NCHW fp32 input of the
-    MFMA kernels' shape is transposed to channel-last by the library's tiled transpose; anything else is read as NCHW."""
+def _layout(x, shape):
+    """(tensor whose memory the kernels read, nhwc flag): a channel-last input is read in place; an NCHW input whose channel-
+    last route is the MFMA kernel is transposed by the library's tiled transpose; anything else is read as NCHW.  ``shape``:
+    ``_args`` of the call, the integers the library's route table (csrc/deform_conv_route.h) is asked with."""
     B, C, H, W = x.shape
     if x.is_contiguous():
-        if _fast_shape(x, weight, offset_groups) and C > 1 and H * W > 1:
+        # (about the tensor, not the route: a copy that changes something, within the tiled transpose's own grid limits)
+        if (x.is_cuda and C > 1 and H * W > 1 and B <= 65535 and (H * W + 63) // 64 <= 65535
+                and _lib.dc_route(_lib.ROUTE_FORWARD, x.element_size(), *shape, 1, 1) == "fwd_mfma"):
             t = _transpose(x, B, C, H * W)                                  # memory [B, H*W, C]
             return t.view(B, H, W, C).permute(0, 3, 1, 2), 1
         return x, 0
@@ -75,13 +71,14 @@ class DeformConv2dFunction(Function):
     @staticmethod
     def forward(ctx, input, offset, weight, bias, stride, padding, dilation, offset_groups):
         conf = (stride, padding, dilation, offset_groups)
-        x, nhwc = _layout(input, weight, offset_groups)
+        shape = _args(input, weight, conf)
+        x, nhwc = _layout(input, shape)
         offset, weight = offset.contiguous(), weight.contiguous()
         bias = None if bias is None else bias.contiguous()
         B, Co = x.shape[0], weight.shape[0]
         out = torch.empty((B, Co, offset.shape[2], offset.shape[3]), dtype=x.dtype, device=x.device)
         sfx = _lib.suffix(x.dtype)
-        args = _args(x, weight, conf) + [nhwc, out.data_ptr()]
+        args = shape + [nhwc, out.data_ptr()]
         bias_ptr = None if bias is None else bias.data_ptr()
         if x.is_cuda:
             with torch.cuda.device(x.device):
@@ -128,12 +125,13 @@ def permute_weight(weight):
     return weight.detach().permute(2, 3, 0, 1).reshape(kh * kw, Co, C).contiguous()
 
 
-def half_kernel_serves(input, weight, offset_groups):
-    """True when a 16-bit CUDA call of these shapes goes to dc_fwd_mfma_half (given an aligned or copied input)."""
-    C, Co = input.shape[1], weight.shape[0]
-    return (input.is_cuda and input.dtype in _HALF and offset_groups == 1 and C >= 16 and C % 16 == 0 and Co >= 32
-            and Co % 32 == 0 and Co <= 65535 * 128 and input.numel() > 0
-            and os.environ.get("MVDETR_DEFORM_CONV_HALF", "1") != "0")
+def half_kernel_serves(input, weight, offset_groups, stride=(1, 1), padding=(0, 0), dilation=(1, 1), shape=None):
+    """True when a 16-bit CUDA call of these shapes and convolution parameters goes to the 16-bit entry (given an aligned or
+    copied input): to dc_fwd_mfma_half, or to its refusal of a shape no entry takes (the exception is then the entry's, as it
+    always was).  ``shape``: ``_args`` of the call where the caller has them."""
+    shape = shape or _args(input, weight, (stride, padding, dilation, offset_groups))
+    return (input.is_cuda and input.dtype in _HALF and os.environ.get("MVDETR_DEFORM_CONV_HALF", "1") != "0"
+            and _lib.dc_route(_lib.ROUTE_FORWARD_HALF, 2, *shape, 1, 1) in ("fwd_mfma_half", "invalid_value"))
 
 
 def _forward_half(input, offset, weight, bias, conf, relu=False, out=None, weight_t=None):
@@ -144,7 +142,8 @@ def _forward_half(input, offset, weight, bias, conf, relu=False, out=None, weigh
         raise RuntimeError("deform_conv2d: float16 / bfloat16 calls are forward-only (inference): a tensor requires grad; "
                            "call under torch.no_grad() or use float32")
     B, Co, (Ho, Wo) = input.shape[0], weight.shape[0], offset.shape[2:]
-    x, ok = input, half_kernel_serves(input, weight, G)
+    shape = _args(input, weight, conf)
+    x, ok = input, half_kernel_serves(input, weight, G, shape=shape)
     if ok:
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
@@ -164,7 +163,7 @@ def _forward_half(input, offset, weight, bias, conf, relu=False, out=None, weigh
     if out is None:
         out = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
     out_batch_stride = out.stride(0) if B > 1 else Co * Ho * Wo
-    args = _args(x, weight, conf) + [1, int(bool(relu)), out_batch_stride, out.data_ptr()]
+    args = shape + [1, int(bool(relu)), out_batch_stride, out.data_ptr()]
     with torch.cuda.device(x.device):
         rc = getattr(_lib.lib(), f"mvdetr_deform_conv2d_forward_{_lib.suffix(x.dtype, half_ok=True)}")(
             _lib.current_stream_ptr(x.device), x.data_ptr(), offset.data_ptr(), weight_t.data_ptr(),

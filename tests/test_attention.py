@@ -464,4 +464,4 @@ def test_abi_version_and_symbols():
     assert _lib.ABI_VERSION == 18 and _lib.lib().mvdetr_ops_abi_version() == 18
     assert _lib.lib().mvdetr_attention_workspace_bytes(2, 8, 100, 50, 16, 4) == 2 * 8 * 100 * 4
     names = [n for n in _lib.SIGNATURES if "attention" in n]
-    assert len(names) == 11 and np.all([hasattr(_lib.lib(), n) for n in names])
+    assert len(names) == 12 and np.all([hasattr(_lib.lib(), n) for n in names])
