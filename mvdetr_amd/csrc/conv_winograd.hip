@@ -9,7 +9,7 @@
 //   winograd_weights_f32   U[p][c][k] = (G g G^T)[xi][nu], formed in fp64 and rounded once; runs once per weight tensor.
 //   conv3x3_winograd_f32   one launch: a unit of work is 64 tiles x 64 output channels x all 16 positions, run by a workgroup
 //                          of 4 waves.
-//       * the grid is persistent: G = min(units, CUs) workgroups (131 KB of LDS: one per CU), workgroup g runs the units
+//       * the grid is persistent: G = min(units, CUs) workgroups (138 KB of LDS: one per CU), workgroup g runs the units
 //         g, g + G, ... in that order -- no counter, no atomics.  Its chunk pipeline runs through all of them: the staging
 //         side, two chunks ahead, has its own (unit, chunk) cursor, so the input loads and LDS-DMA of a unit's first chunks
 //         are in flight while the unit before it is stored, and only the first unit pays a cold prologue;
@@ -22,11 +22,14 @@
 //         of one tile from 16 8-byte loads), the U slice of the chunk is staged beside it; two LDS buffers, one barrier per
 //         chunk.  With one wave per SIMD every instruction that is not an MFMA costs its issue slots in full (measured:
 //         docs/notes/conv_winograd.md), so the loop is built to need few of them -- buffer loads that return zero outside
-//         the image, LDS rows of 256 bytes reached by instruction offsets, scalar LDS-DMA addressing -- and deals them
-//         out one LDS read and one piece of the other work behind every MFMA;
+//         the image, the four positions of a row of a transformed tile as one 16-byte LDS slot (one ds_write_b128, one
+//         ds_read_b128), every LDS row reached by an instruction offset, LDS-DMA of U in the buffer form with scalar
+//         addressing -- and deals them out at most one LDS read and one piece of the other work behind every MFMA;
 //       * dilation d: the convolution is d*d independent undilated ones on the sub-lattices (y mod d, x mod d); a tile is
-//         (image, sub-lattice, tile row, tile column) and its pixels are d apart -- no copies.  Every sub-lattice gets the
-//         tile grid of the largest one; pixels outside the image read as zero and are never stored.
+//         (image, sub-lattice, tile row, tile column) and its pixels are d apart -- no copies.  Every sub-lattice has its
+//         own tile grid, ceil(rows / 2) x ceil(columns / 2) of its own extent: an image's tiles form one TY x TX grid, the
+//         sub-lattice rows stacked along Y and the sub-lattice columns along X, with no tile wholly outside the image.  A
+//         tile may still hang over the edge by one pixel, which reads as zero and is never stored.
 //   No atomics, no split over the input channels: the result is deterministic.
 #include "bn_epilogue.h"
 #include "common.h"
@@ -47,25 +50,32 @@ namespace wino {
 constexpr int TILES = 64;                  // 2x2 output tiles per workgroup
 constexpr int KB = 64;                     // output channels per workgroup
 constexpr int CC = 8;                      // input channels per chunk
-constexpr int VROW = TILES;                // floats per (position, channel) row of V: 256 bytes, so rows are reached by the
-                                           // st64 offsets of ds_read2 / ds_write2; the column of tile t in the rows of
-                                           // channel pair cp is t ^ 8 cp, which keeps the four channel pairs that one
-                                           // half-wave writes together on different banks
-constexpr int V_FLOATS = 16 * CC * VROW;   // 8,192
+// V in LDS is [channel 8][xi 4][column 72][nu 4]: the four nu of a row xi of one (tile, channel) are one 16-byte slot, written
+// by one ds_write_b128 and read by one ds_read_b128.  The column of tile t in the rows of channel pair cp is t + 2 cp (72
+// columns: 8 of padding), which keeps the four channel pairs that eight lanes write together on different banks and is
+// an instruction offset where it is read (the channel pair is the k-step there); xi and the channel are instruction
+// offsets too, so the writes, the A reads and the B reads take one address register each.
+constexpr int VCOLS = TILES + 8;
+constexpr int VROW = VCOLS * 4;            // floats per (channel, xi) row of V: 1,152 bytes
+constexpr int V_FLOATS = CC * 4 * VROW;    // 9,216
 constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
-constexpr int BUF_FLOATS = V_FLOATS + U_FLOATS;
+constexpr int BUF_FLOATS = U_FLOATS + V_FLOATS;   // U first: every instruction offset of both stays below 64 KB (V) and
+                                                  // 255 rows of 256 bytes (U)
 constexpr int TINFO_SLOTS = 4;             // units whose tiles' output descriptors are kept at a time (a power of two)
-constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 8;       // two buffers + the descriptors = 133,120
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 8;       // two buffers + the descriptors = 141,312
 
 // Range of the x buffer resource and the offset of a pixel outside the image (beyond it: the load returns zero)
 constexpr unsigned X_RANGE = 0xFFFFFFF0u, X_OUTSIDE = 0xFFFFFFF8u;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 struct Shape {
     int N, H, W, C, K, d;
-    int th, tw;                            // tile grid of one sub-lattice
-    unsigned tiles;                        // N * d * d * th * tw
+    int py[5], px[5];                      // tile rows (columns) of the sub-lattice rows (columns) before sy (sx): prefix sums of
+                                           // th(sy) = (ceil((H - sy) / d) + 1) / 2, zero where H <= sy; py[sy] = TY for sy >= d
+    int TY, TX;                            // tile grid of one image: all its sub-lattices
+    unsigned tiles;                        // N * TY * TX
     int kblocks;                           // K / 64
     unsigned units;                        // ceil(tiles / 64) * kblocks: 64 tiles x 64 output channels each
 };
@@ -75,20 +85,21 @@ __device__ __forceinline__ bool tile_origin(const Shape &s, unsigned t, int &n, 
 {
     const bool ok = t < s.tiles;
     t = ok ? t : 0;
-    const unsigned tx = t % (unsigned)s.tw;
-    unsigned r = t / (unsigned)s.tw;
-    const unsigned ty = r % (unsigned)s.th;
-    r /= (unsigned)s.th;
-    const unsigned dd = (unsigned)(s.d * s.d);
-    const unsigned sub = r % dd;
-    n = (int)(r / dd);
-    y0 = (int)(sub / (unsigned)s.d + 2 * ty * s.d);
-    x0 = (int)(sub % (unsigned)s.d + 2 * tx * s.d);
+    const int X = (int)(t % (unsigned)s.TX);
+    const unsigned r = t / (unsigned)s.TX;
+    const int Y = (int)(r % (unsigned)s.TY);
+    n = (int)(r / (unsigned)s.TY);
+    // the sub-lattice by three compares against the prefix sums (an empty one has the prefix of the next: never chosen)
+    const int sy = (Y >= s.py[1]) + (Y >= s.py[2]) + (Y >= s.py[3]);
+    const int sx = (X >= s.px[1]) + (X >= s.px[2]) + (X >= s.px[3]);
+    const int ty = Y - (Y >= s.py[3] ? s.py[3] : Y >= s.py[2] ? s.py[2] : Y >= s.py[1] ? s.py[1] : 0);
+    const int tx = X - (X >= s.px[3] ? s.px[3] : X >= s.px[2] ? s.px[2] : X >= s.px[1] ? s.px[1] : 0);
+    y0 = sy + 2 * ty * s.d;
+    x0 = sx + 2 * tx * s.d;
     return ok;
 }
 
 typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void global_void;
 
 // What the output store applies (MODE 0: nothing, and none of this is read).  res has y's [N, H, W, K] geometry.
 struct Epilogue {
@@ -102,7 +113,7 @@ template <int MODE, bool RELU>
 __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restrict__ x, const float *__restrict__ U,
                                                             float *__restrict__ y, const Shape s, const Epilogue ep)
 {
-    // ONE shared array: two {V, U} buffers, then four units' tiles' output descriptors {pixel offset from the unit's first
+    // ONE shared array: two {U, V} buffers, then four units' tiles' output descriptors {pixel offset from the unit's first
     // image, flags}
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int *const tinfo = reinterpret_cast<int *>(lds + 2 * BUF_FLOATS);
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     const int ltile = tid >> 2, cp = tid & 3;
     unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel pair cp
     __amdgpu_buffer_rsrc_t xrsrc;                                             // the unit's image block, in SGPRs
-    const char *ublk;                                                         // the unit's 64-channel slice of U
+    __amdgpu_buffer_rsrc_t ursrc;                                             // the unit's 64-channel slice of U, likewise
     // Entering unit u: its offsets, bases, and the output descriptors of its tiles into slot 'slot' of tinfo.  The staging
     // side is at most two units ahead of the one whose store reads its slot (C = 8: one chunk per unit), and a barrier lies
     // between any store and the write that is four units later: four slots.
@@ -133,7 +144,9 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         int n0, uy, ux;
         tile_origin(s, tb * TILES, n0, uy, ux);
         xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)n0 * H * W * C), 0, (int)X_RANGE, 0x00020000);
-        ublk = reinterpret_cast<const char *>(U + kb * KB);
+        // the slice starts at its first column of U and the range ends with U (the host bounds U below X_RANGE)
+        ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(U + kb * KB), 0, (int)(((unsigned)(16 * C) * K - kb * KB) * 4u),
+                                                  0x00020000);
         int n, y0, x0;
         const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
 #pragma unroll
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
             int tn, ty0, tx0;
             const bool ok = tile_origin(s, tb * TILES + tid, tn, ty0, tx0);
             int flags = 0;
-            // a sub-lattice smaller than the largest one has tiles that start outside the image
+            // every tile starts inside the image; one that hangs over the edge has no second row or column
             if (ok && ty0 < H && tx0 < W) flags = 1 | (tx0 + d < W ? 2 : 0) | (ty0 + d < H ? 4 : 0);
             int *const ti = tinfo + slot * (2 * TILES);
             ti[2 * tid + 0] = (int)((((unsigned)(tn - n0) * H + ty0) * W + tx0) * (unsigned)K);
@@ -175,7 +188,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     // ---- U staging by LDS-DMA: the chunk's [16][8][64] slice is 8 x 16 bytes per lane, LDS image in lane order ---------------
     // float index f = r * 1024 + tid * 4 of the image [p][c][k]:  p = 2 r + (tid >> 7), c = (tid >> 4) & 7, k = (tid & 15) * 4
     const unsigned uoff = ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + (tid & 15) * 4) * 4u;   // bytes
-    const size_t ustep = (size_t)2 * C * K * 4;                               // two positions further per r, bytes
+    const unsigned ustep = 2u * C * K * 4u;                                   // two positions further per r, bytes
 
     // The x loads are raw buffer loads: the uniform base (image block + chunk) travels in SGPRs, the lane's 32-bit byte
     // offset in one VGPR, and a pixel outside the image has an offset past the buffer's range, for which the hardware
@@ -187,10 +200,9 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         raw[e] = __builtin_bit_cast(float2, v);
     };
     auto load_u = [&](int c0, float *ubuf, int r) {
-        const char *const uc = ublk + ((size_t)c0 * K * 4 + r * ustep);       // uniform: scalar arithmetic
-        unsigned o = uoff;
-        asm volatile("" : "+v"(o));                                           // keeps base + zext(offset) beside the load
-        __builtin_amdgcn_global_load_lds((global_void *)(uc + (uint64_t)o), (lds_void *)(ubuf + r * 1024 + wave * 256), 16, 0, 0);
+        // the buffer form, as the x loads: chunk and position pair in the scalar offset, the lane's constant in one VGPR
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_void *)(ubuf + r * 1024 + wave * 256), 16, (int)uoff,
+                                                 (int)((unsigned)c0 * K * 4u + r * ustep), 0, 0);
     };
     // One sixteenth of a chunk's loads: the 16 x loads go first (two per piece), the 8 LDS-DMA of U behind them.
     auto load_piece = [&](int c0, float *ubuf, int q) {
@@ -202,13 +214,13 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         }
     };
 
-    // B^T d B of the lane's tile and channel pair, in 24 pieces that fit between two MFMAs each:
-    //   pieces 6 xi + {0, 1}   the row combinations tx/ty of row xi
-    //   pieces 6 xi + {2..5}   the four values of row xi for both channels -> V[buf][4 xi + nu][2 cp + e][ltile ^ 8 cp]
+    // B^T d B of the lane's tile and channel pair, in 16 pieces that fit between two MFMAs each:
+    //   pieces 4 xi + {0, 1}   the row combinations tx/ty of row xi
+    //   pieces 4 xi + {2, 3}   the four values of row xi of one channel, one 16-byte store -> V[buf][2 cp + e][xi][ltile + 2 cp]
     float tx[4], ty[4];
-    const int v_off = 2 * cp * VROW + (ltile ^ (8 * cp));
+    const int v_off = U_FLOATS + 2 * cp * 4 * VROW + (ltile + 2 * cp) * 4;
     auto xform_piece = [&](float *vbuf, int u) {
-        const int xi = u / 6, s = u % 6;
+        const int xi = u / 4, s = u % 4;
         const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;                 // t = d[ra] -/+ d[rb]
         if (s < 2) {
 #pragma unroll
@@ -220,32 +232,33 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
             }
             return;
         }
-        const int nu = s - 2;
-        float *const v0 = vbuf + v_off + (4 * xi + nu) * CC * VROW;
-        if (nu == 0) { v0[0] = tx[0] - tx[2]; v0[VROW] = ty[0] - ty[2]; }
-        else if (nu == 1) { v0[0] = tx[1] + tx[2]; v0[VROW] = ty[1] + ty[2]; }
-        else if (nu == 2) { v0[0] = tx[2] - tx[1]; v0[VROW] = ty[2] - ty[1]; }
-        else { v0[0] = tx[1] - tx[3]; v0[VROW] = ty[1] - ty[3]; }
+        // (four adds straight into the four registers of the store: the Makefile keeps this file from the SLP vectoriser
+        // and from vector-combine, which pair x with y and then pay four copies per store)
+        const float *const t = s == 2 ? tx : ty;
+        const f32x4 v = {t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]};
+        *reinterpret_cast<f32x4 *>(vbuf + v_off + ((s - 2) * 4 + xi) * VROW) = v;
     };
 
     // ---- the wave's block of the sixteen products -----------------------------------------------------------------------------
     const int wm = wave & 1, wn = wave >> 1;                                  // 32-tile block, 32-channel block
-    int a_off[4];                                                             // k-step s: + (p * CC + 2 s) * VROW
-#pragma unroll
-    for (int st = 0; st < 4; ++st) a_off[st] = (lane >> 5) * VROW + ((wm * 32 + (lane & 31)) ^ (8 * st));
-    const int b_off = V_FLOATS + (lane >> 5) * KB + wn * 32 + (lane & 31);    // + (p * CC + 2 s) * KB
+    // k-step s, row xi: channel 2 s + (lane >> 5), column tile + 2 s: + (8 s + xi) * VROW + 8 s
+    const int a_off = U_FLOATS + (lane >> 5) * 4 * VROW + (wm * 32 + (lane & 31)) * 4;
+    const int b_off = (lane >> 5) * KB + wn * 32 + (lane & 31);             // + (p * CC + 2 s) * KB
     f32x16 acc[16];
 
     // Two sets of operand registers, by the parity of the k-step: while the sixteen MFMAs of one k-step issue, the
-    // operands of the next one are read, one LDS instruction behind every MFMA -- positions p and p + 1 are eight rows
-    // (2,048 bytes) apart in V and in U, which is one ds_read2st64_b32 and no address arithmetic.
+    // operands of the next one are read, at most one LDS instruction behind every MFMA: the four positions of a row xi
+    // of V are one ds_read_b128; positions p and p + 1 are eight rows (2,048 bytes) apart in U, which is one
+    // ds_read2st64_b32 (a lane needs one float of each 16-byte granule of U: nothing wider exists).  Twelve reads a k-step.
     float fa[2][16], fb[2][16];
     auto read_piece = [&](const float *buf, int st, int q) {
-        const int par = st & 1, p = 2 * (q & 7);
-        if (q < 8) {
-            fa[par][p] = buf[a_off[st] + (p * CC + 2 * st) * VROW];
-            fa[par][p + 1] = buf[a_off[st] + ((p + 1) * CC + 2 * st) * VROW];
-        } else {
+        const int par = st & 1;
+        if (q < 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(buf + a_off + (8 * st + q) * VROW + 8 * st);
+#pragma unroll
+            for (int nu = 0; nu < 4; ++nu) fa[par][4 * q + nu] = v[nu];
+        } else if (q < 12) {
+            const int p = 2 * (q - 4);
             fb[par][p] = buf[b_off + (p * CC + 2 * st) * KB];
             fb[par][p + 1] = buf[b_off + ((p + 1) * CC + 2 * st) * KB];
         }
@@ -256,25 +269,26 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     // first k-step
     {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) load_piece(0, lds + V_FLOATS, q);
+        for (int q = 0; q < 16; ++q) load_piece(0, lds, q);
 #pragma unroll
-        for (int u = 0; u < 24; ++u) xform_piece(lds, u);
+        for (int u = 0; u < 16; ++u) xform_piece(lds, u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this wave's LDS-DMA has landed
         __syncthreads();
         advance();
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             read_piece(lds, 0, q);
-            load_piece(sc * CC, lds + BUF_FLOATS + V_FLOATS, q);
+            load_piece(sc * CC, lds + BUF_FLOATS, q);
         }
     }
 
-    // One chunk = four groups of sixteen MFMAs (k-steps 0..3), one MFMA per position, and behind every MFMA one LDS read of
-    // the next k-step's operands plus one piece of the other work.  With one wave per SIMD nothing else hides the issue
-    // slots of that other work (profiles/conv_winograd_loop_ab.txt), so it is spread evenly and kept short:
+    // One chunk = four groups of sixteen MFMAs (k-steps 0..3), one MFMA per position, and behind the first twelve MFMAs of a
+    // group one LDS read of the next k-step's operands, plus one piece of the other work where there is some.  With one
+    // wave per SIMD nothing else hides the issue slots of that other work (profiles/conv_winograd_loop_ab.txt), so it is
+    // spread evenly and kept short:
     //   k-step 0   nothing else: the next chunk's loads, issued a group earlier, get this group too (2,048 cycles)
-    //   k-step 1   the first half of the next chunk's B^T d B and its LDS writes
-    //   k-step 2   the second half
+    //   k-step 1   the first half of the next chunk's B^T d B and its LDS writes, behind the last eight MFMAs
+    //   k-step 2   the second half, behind the first eight
     //   barrier    every wave's V writes and LDS-DMA of the next chunk are done, all reads of this chunk are done
     //   k-step 3   its reads are the NEXT chunk's k-step 0; the loads of the chunk after it, into the buffer this chunk left
     // The loop runs over the positions (unit, chunk) of ALL the workgroup's units, and the staging side, two positions
@@ -304,14 +318,14 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         for (int p = 0; p < 16; ++p) {
             mfma(p, 1);
             read_piece(cur, 2, p);
-            if (p >= 4) xform_piece(nxt, p - 4);
+            if (p >= 8) xform_piece(nxt, p - 8);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
             mfma(p, 0);
             read_piece(cur, 3, p);
-            if (p < 12) xform_piece(nxt, 12 + p);
+            if (p < 8) xform_piece(nxt, 8 + p);
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -320,7 +334,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         for (int p = 0; p < 16; ++p) {
             mfma(p, 1);
             read_piece(nxt, 0, p);
-            load_piece(sc * CC, cur + V_FLOATS, p);
+            load_piece(sc * CC, cur, p);
             __builtin_amdgcn_sched_barrier(0);
         }
         par ^= 1;
@@ -497,6 +511,9 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C is a multiple of 8, so the bound keeps every
     // offset below 2^32 - 64, under the range of the kernel's x buffer (wino::X_RANGE)
     if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
+    // U is staged through a buffer resource too, with 32-bit byte offsets from the slice's first column: 64 C K bytes
+    // (mvdetr_winograd_weights_f32 makes no U above 2^26 elements of (c, k))
+    if ((int64_t)C * K >= (int64_t)1 << 26) return (int)hipErrorNotSupported;
     if (mode >= 2) {
         // the residual is read while other workgroups store y: their byte ranges may not meet
         const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep.res), y0 = reinterpret_cast<uintptr_t>(y);
@@ -506,9 +523,15 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     if (N == 0) return 0;
     Shape s;
     s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
-    s.th = ((H + dilation - 1) / dilation + 1) / 2;
-    s.tw = ((W + dilation - 1) / dilation + 1) / 2;
-    const int64_t tiles = (int64_t)N * dilation * dilation * s.th * s.tw;
+    // every sub-lattice's own tile grid: th(sy) = (ceil((H - sy) / d) + 1) / 2 tile rows, none where H <= sy
+    s.py[0] = s.px[0] = 0;
+    for (int i = 0; i < 4; ++i) {
+        s.py[i + 1] = s.py[i] + (i < dilation && i < H ? ((H - i + dilation - 1) / dilation + 1) / 2 : 0);
+        s.px[i + 1] = s.px[i] + (i < dilation && i < W ? ((W - i + dilation - 1) / dilation + 1) / 2 : 0);
+    }
+    s.TY = s.py[4];
+    s.TX = s.px[4];
+    const int64_t tiles = (int64_t)N * s.TY * s.TX;
     s.kblocks = K / KB;
     const int64_t blocks = (tiles + TILES - 1) / TILES * s.kblocks;
     if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
