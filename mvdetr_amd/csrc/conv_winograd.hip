@@ -9,10 +9,14 @@
 //   winograd_weights_f32   U[p][c][k] = (G g G^T)[xi][nu], formed in fp64 and rounded once; runs once per weight tensor.
 //   conv3x3_winograd_f32   one launch: a unit of work is 64 tiles x 64 output channels x all 16 positions, run by a workgroup
 //                          of 4 waves.
-//       * the grid is persistent: G = min(units, CUs) workgroups (138 KB of LDS: one per CU), workgroup g runs the units
+//       * the grid is persistent: G = min(units, CUs) workgroups (140 KB of LDS: one per CU), workgroup g runs the units
 //         g, g + G, ... in that order -- no counter, no atomics.  Its chunk pipeline runs through all of them: the staging
 //         side, two chunks ahead, has its own (unit, chunk) cursor, so the input loads and LDS-DMA of a unit's first chunks
-//         are in flight while the unit before it is stored, and only the first unit pays a cold prologue;
+//         are in flight while the unit before it is stored, and only the first unit pays a cold prologue.  Only the first
+//         unit pays divisions too: the host splits the stride of G units into columns, rows and images of the tile grid, and
+//         a workgroup's next unit follows by addition;
+//       * the store is four buffer stores per accumulator register at byte offsets from a per-tile descriptor in LDS, an
+//         element outside the image at an offset that saturates beyond the buffer's range: no branches, no 64-bit addresses;
 //       * every wave owns a 32-tile x 32-channel block of ALL sixteen products: 16 accumulators of v_mfma_f32_32x32x2_f32 =
 //         256 registers per lane (one wave per SIMD; the fp32 MFMA reaches its issue rate from one wave with independent
 //         accumulators), so A^T M A happens in registers -- position p of a (tile, channel) sits in the same lane and
@@ -62,10 +66,13 @@ constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
 constexpr int BUF_FLOATS = U_FLOATS + V_FLOATS;   // U first: every instruction offset of both stays below 64 KB (V) and
                                                   // 255 rows of 256 bytes (U)
 constexpr int TINFO_SLOTS = 4;             // units whose tiles' output descriptors are kept at a time (a power of two)
-constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 8;       // two buffers + the descriptors = 141,312
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 16;      // two buffers + the descriptors = 143,360
 
 // Range of the x buffer resource and the offset of a pixel outside the image (beyond it: the load returns zero)
 constexpr unsigned X_RANGE = 0xFFFFFFF0u, X_OUTSIDE = 0xFFFFFFF8u;
+// An output element that is not stored, in a tile's descriptor: the lane's channel is added with unsigned saturation, so it
+// stays beyond every range, and a buffer store (or a residual load) at it does nothing
+constexpr unsigned Y_NONE = 0xFFFFFFFFu;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -78,17 +85,38 @@ struct Shape {
     unsigned tiles;                        // N * TY * TX
     int kblocks;                           // K / 64
     unsigned units;                        // ceil(tiles / 64) * kblocks: 64 tiles x 64 output channels each
+    // A workgroup's next unit is G units on (G: the grid): its channel block moves by gr = G % kblocks, and its tile
+    // block by G / kblocks, one more where the channel block wraps.  Those two strides of 64 * (G / kblocks + i) tiles
+    // as (columns, rows, images) of the tile grid, columns < TX and rows < TY: a position follows by addition.
+    int gr;
+    int dX0, dY0, dn0, dX1, dY1, dn1;
 };
 
-// Where tile `t` sits: image, top-left OUTPUT pixel (y0, x0); false past the last tile.
-__device__ __forceinline__ bool tile_origin(const Shape &s, unsigned t, int &n, int &y0, int &x0)
+// Where tile `t` sits in the tile grid: column X, row Y, image n (n >= N past the last tile).  Two divisions: once per
+// workgroup and lane, for its first unit.
+__device__ __forceinline__ void tile_grid(const Shape &s, unsigned t, int &X, int &Y, int &n)
 {
-    const bool ok = t < s.tiles;
-    t = ok ? t : 0;
-    const int X = (int)(t % (unsigned)s.TX);
+    X = (int)(t % (unsigned)s.TX);
     const unsigned r = t / (unsigned)s.TX;
-    const int Y = (int)(r % (unsigned)s.TY);
+    Y = (int)(r % (unsigned)s.TY);
     n = (int)(r / (unsigned)s.TY);
+}
+
+// The same tile of the workgroup's next unit (carry: its channel block wrapped), by addition
+__device__ __forceinline__ void tile_step(const Shape &s, bool carry, int &X, int &Y, int &n)
+{
+    X += carry ? s.dX1 : s.dX0;
+    const bool cx = X >= s.TX;
+    X -= cx ? s.TX : 0;
+    Y += (carry ? s.dY1 : s.dY0) + (cx ? 1 : 0);
+    const bool cy = Y >= s.TY;
+    Y -= cy ? s.TY : 0;
+    n += (carry ? s.dn1 : s.dn0) + (cy ? 1 : 0);
+}
+
+// Top-left OUTPUT pixel (y0, x0) of the tile at (X, Y) of the tile grid
+__device__ __forceinline__ void tile_pixel(const Shape &s, int X, int Y, int &y0, int &x0)
+{
     // the sub-lattice by three compares against the prefix sums (an empty one has the prefix of the next: never chosen)
     const int sy = (Y >= s.py[1]) + (Y >= s.py[2]) + (Y >= s.py[3]);
     const int sx = (X >= s.px[1]) + (X >= s.px[2]) + (X >= s.px[3]);
@@ -96,7 +124,6 @@ __device__ __forceinline__ bool tile_origin(const Shape &s, unsigned t, int &n, 
     const int tx = X - (X >= s.px[3] ? s.px[3] : X >= s.px[2] ? s.px[2] : X >= s.px[1] ? s.px[1] : 0);
     y0 = sy + 2 * ty * s.d;
     x0 = sx + 2 * tx * s.d;
-    return ok;
 }
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -113,10 +140,11 @@ template <int MODE, bool RELU>
 __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restrict__ x, const float *__restrict__ U,
                                                             float *__restrict__ y, const Shape s, const Epilogue ep)
 {
-    // ONE shared array: two {U, V} buffers, then four units' tiles' output descriptors {pixel offset from the unit's first
-    // image, flags}
+    // ONE shared array: two {U, V} buffers, then four units' tiles' output descriptors: the byte offsets of a tile's four
+    // outputs from the unit's first image, channel 0 of the unit's block, Y_NONE for one that is not stored
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    int *const tinfo = reinterpret_cast<int *>(lds + 2 * BUF_FLOATS);
+    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+    u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               // uniform: LDS-DMA targets by scalar arithmetic
@@ -135,38 +163,56 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel pair cp
     __amdgpu_buffer_rsrc_t xrsrc;                                             // the unit's image block, in SGPRs
     __amdgpu_buffer_rsrc_t ursrc;                                             // the unit's 64-channel slice of U, likewise
-    // Entering unit u: its offsets, bases, and the output descriptors of its tiles into slot 'slot' of tinfo.  The staging
-    // side is at most two units ahead of the one whose store reads its slot (C = 8: one chunk per unit), and a barrier lies
-    // between any store and the write that is four units later: four slots.
-    auto enter_unit = [&](unsigned u, int slot) {
-        const int kb = (int)(u % (unsigned)s.kblocks);
-        const unsigned tb = u / (unsigned)s.kblocks;
-        int n0, uy, ux;
-        tile_origin(s, tb * TILES, n0, uy, ux);
+    // A unit's place: its channel block and the tile-grid position of its first tile (uniform: SGPRs), one for the staging
+    // side and one for the store.  Found by division for the workgroup's first unit, by addition for every other: the
+    // next unit is G units on, whose stride over the tile grid the host has split into columns, rows and images.
+    struct Place { int kb, X, Y, n; };
+    auto next_unit = [&](Place &p) {
+        p.kb += s.gr;
+        const bool carry = p.kb >= s.kblocks;
+        p.kb -= carry ? s.kblocks : 0;
+        tile_step(s, carry, p.X, p.Y, p.n);
+        return carry;
+    };
+    Place sp, cpl;                                                            // staging side, compute side
+    sp.kb = (int)(blockIdx.x % (unsigned)s.kblocks);
+    tile_grid(s, blockIdx.x / (unsigned)s.kblocks * TILES, sp.X, sp.Y, sp.n);
+    cpl = sp;
+    int lX, lY, ln;                                                           // the loader's tile of the staged unit
+    tile_grid(s, blockIdx.x / (unsigned)s.kblocks * TILES + ltile, lX, lY, ln);
+    // Entering the staged unit: its offsets, bases, and the output descriptors of its tiles into slot 'slot' of tinfo.  The
+    // staging side is at most two units ahead of the one whose store reads its slot (C = 8: one chunk per unit), and a
+    // barrier lies between any store and the write that is four units later: four slots.
+    auto enter_unit = [&](int slot) {
+        const int n0 = sp.n;
         xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)n0 * H * W * C), 0, (int)X_RANGE, 0x00020000);
         // the slice starts at its first column of U and the range ends with U (the host bounds U below X_RANGE)
-        ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(U + kb * KB), 0, (int)(((unsigned)(16 * C) * K - kb * KB) * 4u),
-                                                  0x00020000);
-        int n, y0, x0;
-        const bool tvalid = tile_origin(s, tb * TILES + ltile, n, y0, x0);
+        ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(U + sp.kb * KB), 0,
+                                                  (int)(((unsigned)(16 * C) * K - sp.kb * KB) * 4u), 0x00020000);
+        int y0, x0;
+        tile_pixel(s, lX, lY, y0, x0);
+        const bool tvalid = ln < s.N;                                         // a tile past the last one is in image N or later
+        const unsigned pix = ((unsigned)(ln - n0) * H + y0) * W + x0;         // the tile's first output pixel
+        // pixel (i, j) of the tile's 4x4 input patch: rows and columns by addition, four row and four column tests
+        const unsigned base = (pix * C + 2 * cp) * 4u, cstep = (unsigned)d * C * 4u, rstep = cstep * W;
+        bool oky[4], okx[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int yy = y0 + (i - 1) * d, xx = x0 + (j - 1) * d;
-                const bool ok = tvalid & (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W);     // selects, not branches
-                off[4 * i + j] = ok ? ((((unsigned)(n - n0) * H + yy) * W + xx) * C + 2 * cp) * 4u : X_OUTSIDE;
-            }
+            oky[i] = tvalid & ((unsigned)(y0 + (i - 1) * d) < (unsigned)H);
+            okx[i] = (unsigned)(x0 + (i - 1) * d) < (unsigned)W;
         }
-        if (tid < TILES) {
-            int tn, ty0, tx0;
-            const bool ok = tile_origin(s, tb * TILES + tid, tn, ty0, tx0);
-            int flags = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned row = base + (unsigned)(i - 1) * rstep;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) off[4 * i + j] = (oky[i] & okx[j]) ? row + (unsigned)(j - 1) * cstep : X_OUTSIDE;   // selects
+        }
+        if (cp == 0) {
             // every tile starts inside the image; one that hangs over the edge has no second row or column
-            if (ok && ty0 < H && tx0 < W) flags = 1 | (tx0 + d < W ? 2 : 0) | (ty0 + d < H ? 4 : 0);
-            int *const ti = tinfo + slot * (2 * TILES);
-            ti[2 * tid + 0] = (int)((((unsigned)(tn - n0) * H + ty0) * W + tx0) * (unsigned)K);
-            ti[2 * tid + 1] = flags;
+            const bool in = tvalid & (y0 < H) & (x0 < W), right = in & (x0 + d < W), below = in & (y0 + d < H);
+            const unsigned o = pix * (unsigned)K * 4u, dx = (unsigned)d * K * 4u, dy = dx * W;
+            tinfo[slot * TILES + ltile] = u32x4{in ? o : Y_NONE, right ? o + dx : Y_NONE, below ? o + dy : Y_NONE,
+                                                (right & below) ? o + dy + dx : Y_NONE};
         }
     };
     unsigned su = blockIdx.x;                                                 // staging cursor: unit, its ordinal & 3, chunk
@@ -180,10 +226,11 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
             su += G;
             sslot = (sslot + 1) & (TINFO_SLOTS - 1);
             sc = 0;
-            enter_unit(su, sslot);
+            tile_step(s, next_unit(sp), lX, lY, ln);
+            enter_unit(sslot);
         }
     };
-    enter_unit(su, 0);
+    enter_unit(0);
 
     // ---- U staging by LDS-DMA: the chunk's [16][8][64] slice is 8 x 16 bytes per lane, LDS image in lane order ---------------
     // float index f = r * 1024 + tid * 4 of the image [p][c][k]:  p = 2 r + (tid >> 7), c = (tid >> 4) & 7, k = (tid & 15) * 4
@@ -349,11 +396,20 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
 
         // ---- behind the unit's last chunk: A^T M A in registers, then the stores -------------------------------------------------
         // The operands of the next position's first k-step are already in registers and its loads in flight.
-        const int kb = (int)(cu % (unsigned)s.kblocks);
-        int n0, uy, ux;
-        tile_origin(s, cu / (unsigned)s.kblocks * TILES, n0, uy, ux);
-        float *const yblk = y + (size_t)n0 * H * W * K + kb * KB;
-        const int *const ti = tinfo + cslot * (2 * TILES);
+        const int kb = cpl.kb, n0 = cpl.n;
+        // y (and the residual) through a buffer resource that starts at the unit's first image and channel and ends with
+        // the tensor: a lane's byte offset is its tile's descriptor plus its channel, and Y_NONE plus anything saturates
+        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+        const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
+        const __amdgpu_buffer_rsrc_t yrsrc =
+            __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+        // accumulator register r holds tile wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5): an instruction offset
+        const u32x4 *const ti = tinfo + cslot * TILES + wm * 32 + 4 * (lane >> 5);
+        auto offsets = [&](int r, unsigned (&o4)[4]) {
+            const u32x4 dsc = ti[(r & 3) + 8 * (r >> 2)];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+        };
         // The BatchNorm constants of channel kb * 64 + kcol, folded when the workgroup's channel block changes: once per
         // launch where the grid is a multiple of kblocks.
         if (MODE >= 1 && kb != kb_folded) {
@@ -371,21 +427,14 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         // past the buffer's range, for which nothing is read.  The range ends with the tensor.
         float q[2][4][4];
         __amdgpu_buffer_rsrc_t rrsrc;
-        if (MODE >= 2) {
-            const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
-            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0,
-                                                      (int)(left < X_RANGE ? (unsigned)left : X_RANGE), 0x00020000);
-        }
+        if (MODE >= 2)
+            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
+                                                      0x00020000);
         auto load_res = [&](int b) {
-            const unsigned dx = (unsigned)d * K * 4u, dy = (unsigned)d * W * K * 4u;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                const int r = 4 * b + rr;
-                const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const int flags = ti[2 * t + 1];
-                const unsigned o = ((unsigned)ti[2 * t + 0] + kcol) * 4u;
-                const unsigned o4[4] = {(flags & 1) ? o : X_OUTSIDE, (flags & 3) == 3 ? o + dx : X_OUTSIDE,
-                                        (flags & 5) == 5 ? o + dy : X_OUTSIDE, (flags & 7) == 7 ? o + dy + dx : X_OUTSIDE};
+                unsigned o4[4];
+                offsets(4 * b + rr, o4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     q[b & 1][rr][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
@@ -404,9 +453,8 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
                 load_res(r / 4 + 1);
                 __builtin_amdgcn_sched_barrier(0);                            // issued ahead of the stores of batch r / 4
             }
-            const int t = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); // the accumulator's row = the tile
-            const int flags = ti[2 * t + 1];
-            const unsigned pix = (unsigned)ti[2 * t + 0];
+            unsigned o4[4];                                                   // the accumulator's row = the tile
+            offsets(r, o4);
             // Register r of the sixteen accumulators, read one by one: left to the compiler, an element of an accumulator
             // costs a copy of all its sixteen registers, 4,096 reads per unit where 256 are needed.
             float m[16];
@@ -428,15 +476,11 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
                 y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? qr[2] : 0.f, bs2);
                 y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? qr[3] : 0.f, bs2);
             }
-            float *const o = yblk + pix + kcol;
-            if (flags & 1) {
-                o[0] = y00;
-                if (flags & 2) o[(size_t)d * K] = y01;
-                if (flags & 4) {
-                    o[(size_t)d * W * K] = y10;
-                    if (flags & 2) o[(size_t)d * W * K + (size_t)d * K] = y11;
-                }
-            }
+            // four buffer stores, no branch: one at Y_NONE is dropped
+            const float y4[4] = {y00, y01, y10, y11};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y4[e]), yrsrc, (int)o4[e], 0, 0);
             // one register's sixteen reads at a time, and the accumulators stay where the MFMAs left them: copied out all at
             // once they take the whole VGPR file, and the allocator then spills the loop's operands to make room
 #pragma unroll
@@ -444,6 +488,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
             __builtin_amdgcn_sched_barrier(0);
         }
         cu += G;
+        next_unit(cpl);
         cslot = (cslot + 1) & (TINFO_SLOTS - 1);
     } while (cu < s.units);
     // the loads of the last k-step 3 are nobody's, but an LDS-DMA must not outlive the workgroup's LDS
@@ -549,6 +594,16 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     const int cap = g_winograd_max_workgroups.load();
     unsigned nb = s.units < (unsigned)cus ? s.units : (unsigned)cus;
     if (cap > 0 && nb > (unsigned)cap) nb = (unsigned)cap;
+    // the stride from a workgroup's unit to its next one (nb units on), over the tile grid
+    s.gr = (int)(nb % (unsigned)s.kblocks);
+    const auto stride = [&](int64_t tile_blocks, int &dX, int &dY, int &dn) {
+        const int64_t t = tile_blocks * TILES, r = t / s.TX;
+        dX = (int)(t % s.TX);
+        dY = (int)(r % s.TY);
+        dn = (int)(r / s.TY);
+    };
+    stride(nb / (unsigned)s.kblocks, s.dX0, s.dY0, s.dn0);
+    stride(nb / (unsigned)s.kblocks + 1, s.dX1, s.dY1, s.dn1);
     int rc;
     if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep);
     else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep) : launch<1, false>(st, nb, x, U, y, s, ep);

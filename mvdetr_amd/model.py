@@ -1,8 +1,8 @@
 """Minimal caller of the fusion path: an MVDeTr-shaped detector whose warp and deformable attention
 run on the HIP kernels.  The trunk's and the heads' convolutions are ordinary PyTorch-ROCm, as in the
 reference; in inference the trunk's BatchNorm / ReLU / residual-add / max-pool passes between them run
-fused on HIP kernels (ops/trunk_epilogue.py), and as the modules' own torch ops everywhere else; the wide 3x3
-convolutions of layer3/4 that measured faster that way run as an fp32 Winograd MFMA kernel (ops/conv_winograd.py).
+fused on HIP kernels (ops/trunk_epilogue.py), and as the modules' own torch ops everywhere else; the stride-1 3x3
+convolutions of layer1-4 that measured faster that way run as an fp32 Winograd MFMA kernel (ops/conv_winograd.py).
 
 Mirrors multiview_detector/models/mvdetr.py:74-218 (constructor arithmetic, forward order, output
 tuple) and the dilated ResNet-18 trunk of multiview_detector/models/resnet.py:33-70,120-186

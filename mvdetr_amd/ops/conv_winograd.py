@@ -39,6 +39,23 @@ DILATIONS = (1, 2, 4)
 MIN_PIXELS = 8192
 _min_pixels = MIN_PIXELS
 
+# The layer1/2 families: the same rule (the kernel with the block's epilogue in its store against MIOpen + bn_act, every
+# repetition: profiles/conv_winograd_families_shapes.txt), a table and a floor of their own.  With 1 or 2 blocks of 64
+# channels, one workgroup per CU is 512 / K times as many pixels as above: 65,536 at K = 64, 32,768 at K = 128.  The
+# floor above does not move this one (the models of the existing tests keep torch's layer1/2 convolutions at floor 0);
+# set_winograd_narrow_min_pixels() does.  A (C, K, dilation) that is in FAMILIES has FAMILIES' floor.
+NARROW_FAMILIES: dict = {(64, 64): (1,), (128, 128): (1,)}
+_narrow_min_pixels = MIN_PIXELS
+
+
+def min_pixels(C: int, K: int, dilation: int):
+    """The pixel floor of (C, K, dilation) under the current settings; None for a shape outside both tables."""
+    if dilation in FAMILIES.get((C, K), ()):
+        return _min_pixels
+    if dilation in NARROW_FAMILIES.get((C, K), ()):
+        return _narrow_min_pixels * 512 // K
+    return None
+
 
 def set_trunk_winograd(on: bool) -> bool:
     """Switch the Winograd convolutions on or off for this process (default on; ``MVDETR_TRUNK_WINOGRAD=0`` starts with
@@ -66,10 +83,18 @@ def winograd_epilogue_enabled() -> bool:
 
 
 def set_winograd_min_pixels(pixels: int) -> int:
-    """The pixel floor of winograd_conv3x3_available() (MIN_PIXELS by default); returns the previous one.  For tests, which
-    run the model on small images."""
+    """The pixel floor of winograd_conv3x3_available() for FAMILIES (MIN_PIXELS by default); returns the previous one.  For
+    tests, which run the model on small images."""
     global _min_pixels
     prev, _min_pixels = _min_pixels, int(pixels)
+    return prev
+
+
+def set_winograd_narrow_min_pixels(pixels: int) -> int:
+    """The same for NARROW_FAMILIES, whose floor is ``pixels * 512 / K`` (MIN_PIXELS by default: 65,536 at K = 64, 32,768 at
+    K = 128; 0: none); returns the previous setting."""
+    global _narrow_min_pixels
+    prev, _narrow_min_pixels = _narrow_min_pixels, int(pixels)
     return prev
 
 
@@ -128,14 +153,13 @@ def _structure_ok(x, conv) -> bool:
 def winograd_conv3x3_available(x: torch.Tensor, conv: nn.Module) -> bool:
     """True when the model runs ``conv`` on ``x`` through the Winograd kernel: the switch is on, CUDA fp32 dense
     channel-last x, a plain nn.Conv2d with a 3x3 kernel, stride 1, groups 1, padding == dilation in {1, 2, 4}, no bias,
-    zero padding, (C, K, dilation) in a family that measured faster than MIOpen, nothing that needs autograd,
-    ``torch.backends.cudnn.deterministic`` off (a caller who asked for the library's deterministic solvers keeps torch's
-    convolution) and at least the pixel floor of output pixels."""
+    zero padding, (C, K, dilation) in a family that measured faster than MIOpen (FAMILIES or NARROW_FAMILIES), nothing that
+    needs autograd, ``torch.backends.cudnn.deterministic`` off (a caller who asked for the library's deterministic solvers
+    keeps torch's convolution) and at least the family's pixel floor of output pixels (min_pixels())."""
     if not (_enabled and _structure_ok(x, conv)) or torch.backends.cudnn.deterministic:
         return False
-    if conv.dilation[0] not in FAMILIES.get((conv.in_channels, conv.out_channels), ()):
-        return False
-    return x.shape[0] * x.shape[2] * x.shape[3] >= _min_pixels
+    floor = min_pixels(conv.in_channels, conv.out_channels, conv.dilation[0])
+    return floor is not None and x.shape[0] * x.shape[2] * x.shape[3] >= floor
 
 
 class _Entry:

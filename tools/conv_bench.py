@@ -1,4 +1,5 @@
-"""The trunk's eight layer3/4 3x3 convolutions at Wildtrack size (7 x 90 x 160 pixels, fp32, channel-last): torch's
+"""The trunk's stride-1 3x3 convolutions at Wildtrack size (layer2-4: 7 x 90 x 160 pixels, layer1: 7 x 180 x 320; fp32,
+channel-last): torch's
 convolution (cudnn.benchmark = True, as bench.py sets: MIOpen picks by measurement) against the Winograd F(2x2,3x3)
 MFMA kernel, interleaved in one process, HIP events.
 
@@ -22,9 +23,10 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SHAPES = [  # name, C, K, dilation
-    ("layer3.0.conv1", 128, 256, 1), ("layer3.x.conv2", 256, 256, 1), ("layer3.1.conv1", 256, 256, 2),
-    ("layer4.0.conv1", 256, 512, 2), ("layer4.x.conv2", 512, 512, 1), ("layer4.1.conv1", 512, 512, 4),
+SHAPES = [  # name, C, K, dilation, pixels (None: --pixels)
+    ("layer3.0.conv1", 128, 256, 1, None), ("layer3.x.conv2", 256, 256, 1, None), ("layer3.1.conv1", 256, 256, 2, None),
+    ("layer4.0.conv1", 256, 512, 2, None), ("layer4.x.conv2", 512, 512, 1, None), ("layer4.1.conv1", 512, 512, 4, None),
+    ("layer1.x.conv1/2", 64, 64, 1, (7, 180, 320)), ("layer2.x.conv1/2", 128, 128, 1, (7, 90, 160)),
 ]
 
 # --epilogue: name, C, K, dilation, the epilogues the trunk runs behind it, pixels (None: --pixels)
@@ -112,11 +114,12 @@ def main():
     if args.epilogue:
         lines, shapes = epilogue_table(args, dev), []
     else:
-        lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, {N} x {H} x {W} pixels, fp32 channel-last, ms per launch "
+        lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, fp32 channel-last, ms per launch "
                  f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",
-                 "# shape               C->K     d  GFLOP   torch min/med/max        winograd min/med/max     TF/s(direct-equivalent)  "
+                 "# shape               C->K     d  pixels       GFLOP   torch min/med/max        winograd min/med/max     TF/s(direct-equivalent)  "
                  "wins  err torch / winograd vs fp64"]
-    for name, C, K, d in shapes:
+    for name, C, K, d, pixels in shapes:
+        N, H, W = pixels or args.pixels
         torch.manual_seed(C + K + d)
         conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
         nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
@@ -135,7 +138,7 @@ def main():
         gflop = 2.0 * N * H * W * C * K * 9 / 1e9
         wins = sum(w < t for w, t in zip(t_w, t_t))
         med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
-        lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {gflop:6.1f}  {min(t_t):6.3f} {med(t_t):6.3f} {max(t_t):6.3f}     "
+        lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {gflop:6.1f}  {min(t_t):6.3f} {med(t_t):6.3f} {max(t_t):6.3f}     "
                      f"{min(t_w):6.3f} {med(t_w):6.3f} {max(t_w):6.3f}     {gflop / med(t_w):7.1f}                  {wins}/{args.reps}   "
                      f"{e_t:.2e} / {e_w:.2e}")
         print(lines[-1], flush=True)
