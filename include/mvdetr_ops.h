@@ -408,6 +408,28 @@ int64_t mvdetr_winograd_launch_count(void);
  * channels.  This caps it at n workgroups for the whole process (0: no cap, the default) and returns the previous cap
  * (additive entry).  For tests, so that small shapes run many units per workgroup; results do not depend on it. */
 int mvdetr_winograd_set_max_workgroups(int n);
+/* The last round's tail (additive entries, the ABI version above is unchanged).  A unit is indivisible, so with G workgroups,
+ * R = units / G and rem = units % G > 0, the last round keeps rem CUs busy for a whole unit time.  Where rem <= G / 2 the
+ * persistent kernel runs the units [0, R G) and a second launch, "conv3x3_winograd_w16_f32", runs the rest as 2 rem HALF
+ * units of 32 tiles x 64 channels (v_mfma_f32_16x16x4_f32, the same order of channels: the same bits).  One convolution
+ * call stays one count of mvdetr_winograd_launch_count and its name stays "conv3x3_winograd_f32".
+ *   mvdetr_winograd_set_tail         0: never; 1: the default -- where rem <= G / 2, on the (C, K, dilation) on which it
+ *                                    measured faster; 2: whenever rem > 0, on every shape (tests).  Returns the previous mode.
+ *   mvdetr_winograd_last_tail_units  the units the last convolution call ran as half units (0: no second launch)
+ *   mvdetr_winograd_plan             without a device: out[6] = {units, G, R, rem, half units, variant} of a call on
+ *                                    `workgroups` CUs under the current cap, tail mode and variant; the refusals of
+ *                                    mvdetr_conv3x3_winograd_f32's shapes
+ * The persistent kernel has two forms with the same units, order of channels and bits: 1, "conv3x3_winograd_f32" proper (4 waves,
+ * 32 tiles x 32 channels per wave on v_mfma_f32_32x32x2_f32, one wave per SIMD), and 2, "conv3x3_winograd_w16x2_f32" (8 waves,
+ * 32 tiles x 16 channels per wave on v_mfma_f32_16x16x4_f32, two waves per SIMD).
+ *   mvdetr_winograd_set_variant      0: the default -- 2 on the (C, K, dilation) on which it measured faster, 1 elsewhere;
+ *                                    1 or 2: that one on every shape (tests, A/B).  Returns the previous setting.
+ *   mvdetr_winograd_last_variant     the form the last convolution call ran (0 before the first) */
+int mvdetr_winograd_set_variant(int variant);
+int mvdetr_winograd_last_variant(void);
+int mvdetr_winograd_set_tail(int mode);
+int mvdetr_winograd_last_tail_units(void);
+int mvdetr_winograd_plan(int N, int H, int W, int C, int K, int dilation, int workgroups, int64_t *out);
 
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------
  * Name of the kernel variant the last forward call ON THIS THREAD dispatched to

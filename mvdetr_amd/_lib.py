@@ -110,6 +110,11 @@ SIGNATURES = {
     "mvdetr_winograd_last_epilogue": ([], ctypes.c_char_p),
     "mvdetr_winograd_launch_count": ([], ctypes.c_int64),
     "mvdetr_winograd_set_max_workgroups": ([_i], _i),
+    "mvdetr_winograd_set_tail": ([_i], _i),
+    "mvdetr_winograd_set_variant": ([_i], _i),
+    "mvdetr_winograd_last_variant": ([], _i),
+    "mvdetr_winograd_last_tail_units": ([], _i),
+    "mvdetr_winograd_plan": ([_i] * 7 + [_vp], _i),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f64": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f16": (_WARP, _i),

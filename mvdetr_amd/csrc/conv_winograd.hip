@@ -34,6 +34,12 @@
 //         own tile grid, ceil(rows / 2) x ceil(columns / 2) of its own extent: an image's tiles form one TY x TX grid, the
 //         sub-lattice rows stacked along Y and the sub-lattice columns along X, with no tile wholly outside the image.  A
 //         tile may still hang over the edge by one pixel, which reads as zero and is never stored.
+//   conv3x3_winograd_w16x2_f32   the same persistent kernel on wave blocks of 32 tiles x 16 channels (v_mfma_f32_16x16x4_f32):
+//                          8 waves, two per SIMD, so that one wave's loads, transform, LDS traffic and waits issue beside the
+//                          other's MFMAs.  The same units, order of channels and bits; the host's table says which of the two a
+//                          (C, K, dilation) runs (mvdetr_winograd_set_variant overrides it).
+//   conv3x3_winograd_w16_f32     HALF units (32 tiles x 64 channels, 4 waves of the same wave block), one per workgroup, for the
+//                          units of a launch's last, mostly empty round: a second launch behind the persistent one.
 //   No atomics, no split over the input channels: the result is deterministic.
 #include "bn_epilogue.h"
 #include "common.h"
@@ -48,6 +54,10 @@ static std::atomic<const char *> g_winograd_last_kernel{"none"};
 static std::atomic<const char *> g_winograd_last_epilogue{"none"};
 static std::atomic<int64_t> g_winograd_launches{0};
 static std::atomic<int> g_winograd_max_workgroups{0};                         // 0: one per CU (mvdetr_winograd_set_max_workgroups)
+static std::atomic<int> g_winograd_tail{1};                                   // mvdetr_winograd_set_tail
+static std::atomic<int> g_winograd_last_tail_units{0};
+static std::atomic<int> g_winograd_variant{0};                                // mvdetr_winograd_set_variant
+static std::atomic<int> g_winograd_last_variant{0};
 
 namespace wino {
 
@@ -495,6 +505,566 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- the half unit: 32 tiles x 64 output channels, for the units of a launch's last, mostly empty round ------------------------
+// The persistent kernel's unit is indivisible, so a remainder of `rem` units keeps rem CUs busy for a whole unit time while
+// the others idle.  This kernel runs a unit as two workgroups of half the tiles each, on twice the CUs in about half the
+// time, and the host (conv_entry) launches it behind the main one for the remainder alone.
+//   * a wave owns 32 tiles x 16 channels of all sixteen products on v_mfma_f32_16x16x4_f32: 16 positions x 2 blocks of 16
+//     tiles = 32 accumulators of 4 registers, 128 per lane.  Position p of a (tile, channel) is again one lane and register
+//     of accumulator p, so A^T M A stays in registers.  Both fp32 MFMAs are fmaf chains in the order of k, and the channels
+//     go by in the same order: the bits of conv3x3_winograd_f32.
+//   * one half unit per workgroup, found by division; no persistence (a tail has at most one workgroup per CU).
+//   * a chunk of 8 channels is two k-steps of 32 MFMAs.  The loader has one (tile, channel) per lane, the channel fastest:
+//     sixteen 4-byte buffer loads, 32 adds, four ds_write_b128; the chunk's U slice is 8 LDS-DMA per lane, as above.
+//   * V in LDS is [channel 8][xi 4][column 40][nu 4], the column of tile t in the rows of channel c being t + 2 (c >> 1).
+//     ds_read_b128 is served in groups of 16 lanes that mix two channels of a k-step (k = lane >> 4): lanes 0-3, 12-15 of
+//     channel k with lanes 4-11 of channel k + 1, on 64 banks.  Those are disjoint only where the two channels have the same
+//     shift, so the shift goes by channel PAIR, and the eight lanes of a ds_write_b128 group (32 banks) meet two by two:
+//     16 LDS cycles for an instruction that takes 13 to issue.
+//   * U in LDS is [p][c][64] with the row of an odd channel rotated by 16 floats: a B operand is one float per lane, lanes
+//     0-15 of channel k and 16-31 of channel k + 1 in one group of ds_read_b32 on 32 banks.  The rotation is free: the
+//     LDS-DMA writes in lane order and the lane chooses what it fetches.
+namespace w16 {
+constexpr int HT = 32;                     // tiles of a half unit
+constexpr int VCOLS = HT + 8;
+constexpr int VROW = VCOLS * 4;            // floats per (channel, xi) row of V: 640 bytes; a channel is 640 floats = 10 x 64 banks
+constexpr int V_FLOATS = CC * 4 * VROW;    // 5,120
+constexpr int BUF_FLOATS = U_FLOATS + V_FLOATS;
+constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + HT * 16;                       // two buffers + the descriptors = 107,008
+}  // namespace w16
+
+// Half unit j of the launch is tile half j & 1 of unit `unit0 + j / 2`; one wholly past the last tile stores nothing.
+template <int MODE, bool RELU>
+__global__ __launch_bounds__(256) void conv3x3_winograd_w16_f32(const float *__restrict__ x, const float *__restrict__ U,
+                                                                float *__restrict__ y, const Shape s, const Epilogue ep,
+                                                                const unsigned unit0)
+{
+    constexpr int HT = w16::HT, VROW = w16::VROW, BUF_FLOATS = w16::BUF_FLOATS;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+    u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               // the wave's quarter of the 64 channels
+    const int C = s.C, K = s.K, d = s.d, H = s.H, W = s.W;
+    const int chunks = C / CC;
+    const unsigned unit = unit0 + (blockIdx.x >> 1);
+    const int kb = (int)(unit % (unsigned)s.kblocks);
+    const unsigned t0 = unit / (unsigned)s.kblocks * TILES + (blockIdx.x & 1) * HT;
+    if (t0 >= s.tiles) return;                                                // uniform: before any barrier
+
+    // ---- the loader's (tile, channel): offsets, bases and the tile's output descriptor, as in conv3x3_winograd_f32 -------
+    const int ltile = tid >> 3, lc = tid & 7;
+    int X0, Y0, n0, lX, lY, ln;
+    tile_grid(s, t0, X0, Y0, n0);
+    tile_grid(s, t0 + ltile, lX, lY, ln);
+    const __amdgpu_buffer_rsrc_t xrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)n0 * H * W * C), 0, (int)X_RANGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float *>(U + kb * KB), 0, (int)(((unsigned)(16 * C) * K - kb * KB) * 4u), 0x00020000);
+    unsigned off[16];                                                         // BYTE offset of pixel (i, j), channel lc
+    {
+        int y0, x0;
+        tile_pixel(s, lX, lY, y0, x0);
+        const bool tvalid = ln < s.N;
+        const unsigned pix = ((unsigned)(ln - n0) * H + y0) * W + x0;
+        const unsigned base = (pix * C + lc) * 4u, cstep = (unsigned)d * C * 4u, rstep = cstep * W;
+        bool oky[4], okx[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            oky[i] = tvalid & ((unsigned)(y0 + (i - 1) * d) < (unsigned)H);
+            okx[i] = (unsigned)(x0 + (i - 1) * d) < (unsigned)W;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned row = base + (unsigned)(i - 1) * rstep;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) off[4 * i + j] = (oky[i] & okx[j]) ? row + (unsigned)(j - 1) * cstep : X_OUTSIDE;
+        }
+        if (lc == 0) {
+            const bool in = tvalid & (y0 < H) & (x0 < W), right = in & (x0 + d < W), below = in & (y0 + d < H);
+            const unsigned o = pix * (unsigned)K * 4u, dx = (unsigned)d * K * 4u, dy = dx * W;
+            tinfo[ltile] = u32x4{in ? o : Y_NONE, right ? o + dx : Y_NONE, below ? o + dy : Y_NONE,
+                                 (right & below) ? o + dy + dx : Y_NONE};
+        }
+    }
+
+    // ---- U by LDS-DMA: float f = r * 1024 + tid * 4 of the LDS image is p = 2 r + (tid >> 7), c = (tid >> 4) & 7, column
+    // (tid & 15) * 4, which holds output channel (column - 16 (c & 1)) mod 64 of the slice
+    const unsigned uoff =
+        ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + ((((tid & 15) * 4) - 16 * ((tid >> 4) & 1)) & 63)) * 4u;
+    const unsigned ustep = 2u * C * K * 4u;
+    float raw[16];
+    auto load_piece = [&](int c0, float *ubuf, int q) {                       // 16 x loads, then the 8 LDS-DMA of U
+        if (q < 16)
+            raw[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, (int)off[q], c0 * 4, 0));
+        else if (q < 24)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_void *)(ubuf + (q - 16) * 1024 + wave * 256), 16, (int)uoff,
+                                                     (int)((unsigned)c0 * K * 4u + (q - 16) * ustep), 0, 0);
+    };
+    // B^T d B of the lane's (tile, channel) in 16 pieces: 4 xi + {0, 1} the row combination of row xi, 4 xi + {2, 3} its four
+    // values and their one 16-byte store -> V[buf][lc][xi][ltile + 2 (lc >> 1)]
+    float t[4];
+    f32x4 v4;
+    const int v_off = U_FLOATS + lc * 4 * VROW + (ltile + 2 * (lc >> 1)) * 4;
+    auto xform_piece = [&](float *vbuf, int u) {
+        const int xi = u / 4, q = u % 4;
+        const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;                 // t = d[ra] -/+ d[rb]
+        if (q < 2) {
+#pragma unroll
+            for (int j = 2 * q; j < 2 * q + 2; ++j) {
+                const float a = raw[4 * ra + j], b = raw[4 * rb + j];
+                t[j] = (xi == 0 || xi == 3) ? a - b : xi == 1 ? a + b : b - a;
+            }
+        } else if (q == 2) {
+            v4[0] = t[0] - t[2];
+            v4[1] = t[1] + t[2];
+        } else {
+            v4[2] = t[2] - t[1];
+            v4[3] = t[1] - t[3];
+            *reinterpret_cast<f32x4 *>(vbuf + v_off + xi * VROW) = v4;
+        }
+    };
+
+    // ---- the wave's block: tile 16 h + (lane & 15) and channel 4 st + (lane >> 4) of k-step st for A, the same channel's
+    // row of U and output channel 16 wave + (lane & 15) for B
+    const int kk = lane >> 4;
+    const int a_off = U_FLOATS + kk * 4 * VROW + ((lane & 15) + 2 * (kk >> 1)) * 4;     // + (16 st + xi) VROW + (16 h + 4 st) 4
+    const int b_off = kk * KB + ((wave * 16 + (lane & 15) + 16 * (kk & 1)) & 63);       // + (p CC + 4 st) KB
+    f32x4 acc[16][2];
+    float fa[2][2][16], fb[2][16];                                            // [set][tile block][p], [set][p]
+    auto read_piece = [&](const float *buf, int st, int set, int q) {         // 8 ds_read_b128, 8 ds_read2st64_b32
+        if (q < 8) {
+            const int xi = q >> 1, h = q & 1;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(buf + a_off + (16 * st + xi) * VROW + (16 * h + 4 * st) * 4);
+#pragma unroll
+            for (int nu = 0; nu < 4; ++nu) fa[set][h][4 * xi + nu] = v[nu];
+        } else if (q < 16) {
+            const int p = 2 * (q - 8);
+            fb[set][p] = buf[b_off + (p * CC + 4 * st) * KB];
+            fb[set][p + 1] = buf[b_off + ((p + 1) * CC + 4 * st) * KB];
+        }
+    };
+
+    // prologue: chunk 0 into buffer 0, then the loads of chunk 1 and the operands of the first k-step
+    int sc = 0;                                                               // the chunk staged next (the last one again past the end)
+    auto advance = [&] { sc = sc + 1 < chunks ? sc + 1 : sc; };
+#pragma unroll
+    for (int q = 0; q < 24; ++q) load_piece(0, lds, q);
+#pragma unroll
+    for (int u = 0; u < 16; ++u) xform_piece(lds, u);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    advance();
+#pragma unroll
+    for (int q = 0; q < 24; ++q) {
+        read_piece(lds, 0, 0, q);
+        load_piece(sc * CC, lds + BUF_FLOATS, q);
+    }
+
+    // One chunk = two k-steps of 32 MFMAs (position p, tile block h: consecutive ones never share an accumulator).
+    //   k-step 0   the reads of k-step 1, then the next chunk's B^T d B and its LDS writes
+    //   barrier    the next chunk's V and U are in LDS, every read of this chunk is done
+    //   k-step 1   the reads of the next chunk's k-step 0, and the loads of the chunk after it into the buffer this one left
+    int par = 0;
+    auto chunk = [&](auto first) {
+        float *const cur = lds + par * BUF_FLOATS;
+        float *const nxt = lds + (par ^ 1) * BUF_FLOATS;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < 32; ++m) {
+            const int p = m >> 1, h = m & 1;
+            acc[p][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0][h][p], fb[0][p], decltype(first)::value ? f32x4{} : acc[p][h], 0, 0, 0);
+            if (m < 16) read_piece(cur, 1, 1, m);
+            else xform_piece(nxt, m - 16);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        advance();
+#pragma unroll
+        for (int m = 0; m < 32; ++m) {
+            const int p = m >> 1, h = m & 1;
+            acc[p][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1][h][p], fb[1][p], acc[p][h], 0, 0, 0);
+            read_piece(nxt, 0, 0, m);
+            load_piece(sc * CC, cur, m);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        par ^= 1;
+    };
+    chunk(std::true_type{});
+    if (chunks > 1) {
+        int ch = 1;
+        do chunk(std::false_type{});
+        while (++ch < chunks);
+    }
+
+    // ---- A^T M A in registers, then the stores: register r of tile block h is tile 16 h + 4 (lane >> 4) + r ----------------
+    const int kcol = wave * 16 + (lane & 15);
+    float bs = 1.f, bt = 0.f, bs2 = 0.f;
+    if (MODE >= 1) {
+        bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
+        if (MODE == 3) {
+            float bt2;
+            bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
+            bt = bt + bt2;
+        }
+    }
+    const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+    const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
+    const __amdgpu_buffer_rsrc_t yrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+    __amdgpu_buffer_rsrc_t rrsrc;
+    if (MODE >= 2)
+        rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
+                                                  0x00020000);
+    const u32x4 *const ti = tinfo + 4 * (lane >> 4);
+    unsigned o4[8][4];
+    float q4[8][4];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const u32x4 dsc = ti[16 * (b >> 2) + (b & 3)];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o4[b][e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+            if (MODE >= 2) q4[b][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[b][e], 0, 0));
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int h = b >> 2, r = b & 3;
+        float s0[4], s1[4];
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            s0[nu] = acc[nu][h][r] + acc[4 + nu][h][r] + acc[8 + nu][h][r];
+            s1[nu] = acc[4 + nu][h][r] - acc[8 + nu][h][r] - acc[12 + nu][h][r];
+        }
+        float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+        float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+        if (MODE >= 1) {
+            constexpr int RES = MODE - 1;
+            y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? q4[b][0] : 0.f, bs2);
+            y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? q4[b][1] : 0.f, bs2);
+            y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? q4[b][2] : 0.f, bs2);
+            y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? q4[b][3] : 0.f, bs2);
+        }
+        const float y4[4] = {y00, y01, y10, y11};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y4[e]), yrsrc, (int)o4[b][e], 0, 0);
+    }
+    // the loads of the last k-step 1 are nobody's, but an LDS-DMA must not outlive the workgroup's LDS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// ---- the 8-wave unit: the persistent kernel on the 16-channel wave block, two waves per SIMD -----------------------------------
+// The unit, the persistent grid, the staging cursor, the descriptors and the store are conv3x3_winograd_f32's.  Wave w owns
+// tile half w / 4 and channel quarter w % 4 of the unit (waves w and w + 4 share a SIMD): 32 tiles x 16 channels of all sixteen
+// products, 128 accumulator registers, pinned to AGPRs; the other 128 registers hold the operands in two sets of eight positions
+// (16 + 8 registers each), the loader's sixteen pixels and offsets.  A chunk is four half k-steps of 16 MFMAs:
+//   k-step 0, positions 0-7     the reads of positions 8-15
+//   k-step 0, positions 8-15    the reads of k-step 1, positions 0-7; the first half of the next chunk's B^T d B
+//   k-step 1, positions 0-7     the reads of positions 8-15; the second half
+//   barrier
+//   k-step 1, positions 8-15    the x loads of the chunk after next, the reads of the next chunk's first set, the LDS-DMA of U
+// The loader has one (tile, channel) per lane as in the half-unit kernel; V keeps 72 columns, U is 4 LDS-DMA per lane.
+template <int MODE, bool RELU>
+__global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *__restrict__ x, const float *__restrict__ U,
+                                                                  float *__restrict__ y, const Shape s, const Epilogue ep)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+    u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = s.C, K = s.K, d = s.d, H = s.H, W = s.W;
+    const int chunks = C / CC;
+    const unsigned G = gridDim.x;
+
+    // ---- the staging side, as in conv3x3_winograd_f32; the loader's lane is one tile and ONE channel ------------------------------
+    const int ltile = tid >> 3, lc = tid & 7;
+    unsigned off[16];
+    __amdgpu_buffer_rsrc_t xrsrc;
+    __amdgpu_buffer_rsrc_t ursrc;
+    struct Place { int kb, X, Y, n; };
+    auto next_unit = [&](Place &p) {
+        p.kb += s.gr;
+        const bool carry = p.kb >= s.kblocks;
+        p.kb -= carry ? s.kblocks : 0;
+        tile_step(s, carry, p.X, p.Y, p.n);
+        return carry;
+    };
+    Place sp, cpl;
+    sp.kb = (int)(blockIdx.x % (unsigned)s.kblocks);
+    tile_grid(s, blockIdx.x / (unsigned)s.kblocks * TILES, sp.X, sp.Y, sp.n);
+    cpl = sp;
+    int lX, lY, ln;
+    tile_grid(s, blockIdx.x / (unsigned)s.kblocks * TILES + ltile, lX, lY, ln);
+    auto enter_unit = [&](int slot) {
+        const int n0 = sp.n;
+        xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)n0 * H * W * C), 0, (int)X_RANGE, 0x00020000);
+        ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(U + sp.kb * KB), 0,
+                                                  (int)(((unsigned)(16 * C) * K - sp.kb * KB) * 4u), 0x00020000);
+        int y0, x0;
+        tile_pixel(s, lX, lY, y0, x0);
+        const bool tvalid = ln < s.N;
+        const unsigned pix = ((unsigned)(ln - n0) * H + y0) * W + x0;
+        const unsigned base = (pix * C + lc) * 4u, cstep = (unsigned)d * C * 4u, rstep = cstep * W;
+        bool oky[4], okx[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            oky[i] = tvalid & ((unsigned)(y0 + (i - 1) * d) < (unsigned)H);
+            okx[i] = (unsigned)(x0 + (i - 1) * d) < (unsigned)W;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned row = base + (unsigned)(i - 1) * rstep;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) off[4 * i + j] = (oky[i] & okx[j]) ? row + (unsigned)(j - 1) * cstep : X_OUTSIDE;
+        }
+        if (lc == 0) {
+            const bool in = tvalid & (y0 < H) & (x0 < W), right = in & (x0 + d < W), below = in & (y0 + d < H);
+            const unsigned o = pix * (unsigned)K * 4u, dx = (unsigned)d * K * 4u, dy = dx * W;
+            tinfo[slot * TILES + ltile] = u32x4{in ? o : Y_NONE, right ? o + dx : Y_NONE, below ? o + dy : Y_NONE,
+                                                (right & below) ? o + dy + dx : Y_NONE};
+        }
+    };
+    unsigned su = blockIdx.x;
+    int sslot = 0, sc = 0;
+    auto advance = [&] {
+        if (sc + 1 < chunks) {
+            ++sc;
+        } else if (su + G < s.units) {
+            su += G;
+            sslot = (sslot + 1) & (TINFO_SLOTS - 1);
+            sc = 0;
+            tile_step(s, next_unit(sp), lX, lY, ln);
+            enter_unit(sslot);
+        }
+    };
+    enter_unit(0);
+
+    // U by LDS-DMA, 4 x 16 bytes per lane: float f = r * 2048 + tid * 4 of the LDS image is p = 4 r + (tid >> 7), c = (tid >> 4) & 7,
+    // column (tid & 15) * 4, which holds output channel (column - 16 (c & 1)) mod 64 (the rotation of the half-unit kernel)
+    const unsigned uoff =
+        ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + ((((tid & 15) * 4) - 16 * ((tid >> 4) & 1)) & 63)) * 4u;
+    const unsigned ustep = 4u * C * K * 4u;
+    float raw[16];
+    auto load_x = [&](int c0, int e) {
+        raw[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, (int)off[e], c0 * 4, 0));
+    };
+    auto load_u = [&](int c0, float *ubuf, int r) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_void *)(ubuf + r * 2048 + wave * 256), 16, (int)uoff,
+                                                 (int)((unsigned)c0 * K * 4u + r * ustep), 0, 0);
+    };
+    float t[4];
+    f32x4 v4;
+    const int v_off = U_FLOATS + lc * 4 * VROW + (ltile + 2 * (lc >> 1)) * 4;
+    auto xform_piece = [&](float *vbuf, int u) {
+        const int xi = u / 4, q = u % 4;
+        const int ra = xi == 0 ? 0 : 1, rb = xi == 3 ? 3 : 2;
+        if (q < 2) {
+#pragma unroll
+            for (int j = 2 * q; j < 2 * q + 2; ++j) {
+                const float a = raw[4 * ra + j], b = raw[4 * rb + j];
+                t[j] = (xi == 0 || xi == 3) ? a - b : xi == 1 ? a + b : b - a;
+            }
+        } else if (q == 2) {
+            v4[0] = t[0] - t[2];
+            v4[1] = t[1] + t[2];
+        } else {
+            v4[2] = t[2] - t[1];
+            v4[3] = t[1] - t[3];
+            *reinterpret_cast<f32x4 *>(vbuf + v_off + xi * VROW) = v4;
+        }
+    };
+
+    // ---- the wave's block ------------------------------------------------------------------------------------------------------
+    const int th = wave >> 2, wq = wave & 3, kk = lane >> 4;
+    const int a_off = U_FLOATS + kk * 4 * VROW + (th * 32 + (lane & 15) + 2 * (kk >> 1)) * 4;
+    const int b_off = kk * KB + ((wq * 16 + (lane & 15) + 16 * (kk & 1)) & 63);
+    f32x4 acc[16][2];
+    float fa[2][2][8], fb[2][8];                                              // [set = position half][tile block][position], [set][position]
+    // the eight reads of half k-step hs (k-step hs >> 1, positions 8 (hs & 1) ..): in the order the MFMAs need them
+    auto read_piece = [&](const float *buf, int hs, int q) {
+        const int st = hs >> 1, half = hs & 1;
+        if ((q & 2) == 0) {
+            const int xl = q >> 2, h = q & 1;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(buf + a_off + (16 * st + 2 * half + xl) * VROW + (16 * h + 4 * st) * 4);
+#pragma unroll
+            for (int nu = 0; nu < 4; ++nu) fa[half][h][4 * xl + nu] = v[nu];
+        } else {
+            const int pl = 4 * (q >> 2) + 2 * (q & 1), p = 8 * half + pl;
+            fb[half][pl] = buf[b_off + (p * CC + 4 * st) * KB];
+            fb[half][pl + 1] = buf[b_off + ((p + 1) * CC + 4 * st) * KB];
+        }
+    };
+    auto mfma = [&](int hs, int m, auto first) {
+        const int half = hs & 1, pl = m >> 1, h = m & 1, p = 8 * half + pl;
+        if (decltype(first)::value) acc[p][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[half][h][pl], fb[half][pl], f32x4{}, 0, 0, 0);
+        else acc[p][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[half][h][pl], fb[half][pl], acc[p][h], 0, 0, 0);
+    };
+
+    // prologue
+    {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) load_x(0, q);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) load_u(0, lds, r);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) xform_piece(lds, u);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        advance();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) load_x(sc * CC, q);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) load_u(sc * CC, lds + BUF_FLOATS, r);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) read_piece(lds, 0, q);
+    }
+
+    const int kcol = wq * 16 + (lane & 15);
+    float bs = 1.f, bt = 0.f, bs2 = 0.f;
+    int kb_folded = -1;
+    unsigned cu = blockIdx.x;
+    int cslot = 0, par = 0;
+    auto chunk = [&](auto first) {
+        advance();
+        float *const cur = lds + par * BUF_FLOATS;
+        float *const nxt = lds + (par ^ 1) * BUF_FLOATS;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            mfma(0, m, first);
+            if (m < 8) read_piece(cur, 1, m);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            mfma(1, m, first);
+            if (m < 8) read_piece(cur, 2, m);
+            else xform_piece(nxt, m - 8);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            mfma(2, m, std::false_type{});
+            if (m < 8) read_piece(cur, 3, m);
+            else xform_piece(nxt, m);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            mfma(3, m, std::false_type{});
+            if (m < 8) {
+                load_x(sc * CC, 2 * m);
+                load_x(sc * CC, 2 * m + 1);
+            } else {
+                read_piece(nxt, 0, m - 8);
+                if (m < 12) load_u(sc * CC, cur, m - 8);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        par ^= 1;
+    };
+    do {
+        chunk(std::true_type{});
+        if (chunks > 1) {
+            int ch = 1;
+            do chunk(std::false_type{});
+            while (++ch < chunks);
+        }
+
+        // ---- the store: conv3x3_winograd_f32's, over 2 tile blocks x 4 registers ------------------------------------------------
+        const int kb = cpl.kb, n0 = cpl.n;
+        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+        const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
+        const __amdgpu_buffer_rsrc_t yrsrc =
+            __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+        // register r of tile block h is tile 32 (w / 4) + 16 h + 4 (lane >> 4) + r
+        const u32x4 *const ti = tinfo + cslot * TILES + th * 32 + 4 * (lane >> 4);
+        auto offsets = [&](int b, unsigned (&o4)[4]) {
+            const u32x4 dsc = ti[16 * (b >> 2) + (b & 3)];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+        };
+        if (MODE >= 1 && kb != kb_folded) {
+            bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
+            if (MODE == 3) {
+                float bt2;
+                bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
+                bt = bt + bt2;
+            }
+            kb_folded = kb;
+        }
+        float q[2][4][4];                                                     // the residual of one tile block, one block ahead
+        __amdgpu_buffer_rsrc_t rrsrc;
+        if (MODE >= 2)
+            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
+                                                      0x00020000);
+        auto load_res = [&](int h) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                unsigned o4[4];
+                offsets(4 * h + rr, o4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    q[h][rr][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
+            }
+        };
+        if (MODE >= 2) {
+            load_res(0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // 18 wait states between the last MFMA's write and the hand-written reads of its registers (more than an 8-pass MFMA needs)
+        asm volatile("s_nop 15\n\ts_nop 3");
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const int h = b >> 2, r = b & 3;
+            if (MODE >= 2 && b == 0) {
+                load_res(1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            unsigned o4[4];
+            offsets(b, o4);
+            float m[16];
+#pragma unroll
+            for (int p = 0; p < 16; ++p) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[p]) : "a"(acc[p][h][r]));
+            float s0[4], s1[4];
+#pragma unroll
+            for (int nu = 0; nu < 4; ++nu) {
+                s0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
+                s1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
+            }
+            float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+            float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+            if (MODE >= 1) {
+                constexpr int RES = MODE - 1;
+                const float *const qr = q[h][r];
+                y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? qr[0] : 0.f, bs2);
+                y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? qr[1] : 0.f, bs2);
+                y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? qr[2] : 0.f, bs2);
+                y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? qr[3] : 0.f, bs2);
+            }
+            const float y4[4] = {y00, y01, y10, y11};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y4[e]), yrsrc, (int)o4[e], 0, 0);
+#pragma unroll
+            for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p][0]), "+a"(acc[p][1]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        cu += G;
+        next_unit(cpl);
+        cslot = (cslot + 1) & (TINFO_SLOTS - 1);
+    } while (cu < s.units);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // U[p = 4 xi + nu][c][k] = (G g G^T)[xi][nu] of weight[k][c][3][3], in fp64, rounded once.  One thread per (c, k).
 __global__ __launch_bounds__(256) void winograd_weights_f32(const float *__restrict__ w, int C, int K, float *__restrict__ U)
 {
@@ -519,17 +1089,32 @@ __global__ __launch_bounds__(256) void winograd_weights_f32(const float *__restr
     }
 }
 
-// One launch of one instantiation (its dynamic-LDS attribute is set once per device)
+// One launch of one instantiation (its dynamic-LDS attribute is set once per device): the persistent kernel over the units
+// [0, s.units) -- variant 1: 4 waves on the 32-channel block, 2: 8 waves on the 16-channel block -- then, where tail_units > 0,
+// the half-unit kernel over the 2 * tail_units halves of the units behind them
 template <int MODE, bool RELU>
-static int launch(hipStream_t st, unsigned blocks, const float *x, const float *U, float *y, const Shape &s, const Epilogue &ep)
+static int launch(hipStream_t st, unsigned blocks, const float *x, const float *U, float *y, const Shape &s, const Epilogue &ep,
+                  int variant, unsigned tail_units)
 {
     static PerDevice<int> lds_attr;
     const int rc = lds_attr.get([] {
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_winograd_f32<MODE, RELU>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        const void *const kernels[3] = {reinterpret_cast<const void *>(conv3x3_winograd_f32<MODE, RELU>),
+                                        reinterpret_cast<const void *>(conv3x3_winograd_w16x2_f32<MODE, RELU>),
+                                        reinterpret_cast<const void *>(conv3x3_winograd_w16_f32<MODE, RELU>)};
+        for (int i = 0; i < 3; ++i) {
+            const int a = (int)hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 2 ? LDS_BYTES : w16::LDS_BYTES);
+            if (a != 0) return a;
+        }
+        return 0;
     });
     if (rc != 0) return rc;
-    hipLaunchKernelGGL((conv3x3_winograd_f32<MODE, RELU>), dim3(blocks), dim3(256), LDS_BYTES, st, x, U, y, s, ep);
+    if (variant == 2)
+        hipLaunchKernelGGL((conv3x3_winograd_w16x2_f32<MODE, RELU>), dim3(blocks), dim3(512), LDS_BYTES, st, x, U, y, s, ep);
+    else
+        hipLaunchKernelGGL((conv3x3_winograd_f32<MODE, RELU>), dim3(blocks), dim3(256), LDS_BYTES, st, x, U, y, s, ep);
+    if (tail_units)
+        hipLaunchKernelGGL((conv3x3_winograd_w16_f32<MODE, RELU>), dim3(2 * tail_units), dim3(256), w16::LDS_BYTES, st, x, U, y, s,
+                           ep, s.units);
     return 0;
 }
 
@@ -540,6 +1125,72 @@ static const char *const kEpilogueNames[4][2] = {
 static bool bn_ok(const BnVectors &b)
 {
     return b.mean && b.var && aligned(b.mean, 4) && aligned(b.var, 4) && aligned(b.gamma, 4) && aligned(b.beta, 4);
+}
+
+// The tile grid of a shape and its units; false where there are 2^31 tiles or units or more
+static bool tile_shape(Shape &s, int N, int H, int W, int C, int K, int dilation)
+{
+    s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
+    // every sub-lattice's own tile grid: th(sy) = (ceil((H - sy) / d) + 1) / 2 tile rows, none where H <= sy
+    s.py[0] = s.px[0] = 0;
+    for (int i = 0; i < 4; ++i) {
+        s.py[i + 1] = s.py[i] + (i < dilation && i < H ? ((H - i + dilation - 1) / dilation + 1) / 2 : 0);
+        s.px[i + 1] = s.px[i] + (i < dilation && i < W ? ((W - i + dilation - 1) / dilation + 1) / 2 : 0);
+    }
+    s.TY = s.py[4];
+    s.TX = s.px[4];
+    const int64_t tiles = (int64_t)N * s.TY * s.TX;
+    s.kblocks = K / KB;
+    const int64_t blocks = (tiles + TILES - 1) / TILES * s.kblocks;
+    if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return false;
+    s.tiles = (unsigned)tiles;
+    s.units = (unsigned)blocks;
+    return true;
+}
+
+// The (C, K, dilation) whose last round runs as half units under tail mode 1: those on which it measured faster in every
+// repetition of tools/conv_bench.py --tail (profiles/conv_winograd_w16_shapes.txt)
+static bool tail_family(int C, int K, int d)
+{
+    static const int table[][3] = {{64, 64, 1}, {128, 128, 1}, {128, 256, 1}, {256, 256, 1}, {256, 256, 2}, {512, 512, 1}};
+    for (const auto &f : table)
+        if (f[0] == C && f[1] == K && f[2] == d) return true;
+    return false;
+}
+
+// The (C, K, dilation) whose persistent launch is the 8-wave kernel under variant mode 0: those on which it measured faster
+// than the 4-wave kernel in every repetition of tools/conv_bench.py --variant (profiles/conv_winograd_w16_shapes.txt)
+static bool variant2_family(int C, int K, int d)
+{
+    static const int table[][3] = {{64, 64, 1},  {128, 128, 1}, {128, 256, 1}, {256, 256, 1},
+                                   {256, 256, 2}, {256, 512, 2}, {512, 512, 1}, {512, 512, 4}};
+    for (const auto &f : table)
+        if (f[0] == C && f[1] == K && f[2] == d) return true;
+    return false;
+}
+
+// How a call is split: G persistent workgroups run the units [0, R G) and, where the rest is a tail, 2 rem half units run
+// the units [R G, units).  Otherwise (half_units = 0) the persistent kernel runs them all.
+struct Plan {
+    unsigned units, G, R, rem, half_units;
+    int variant;                           // 1: conv3x3_winograd_f32, 2: conv3x3_winograd_w16x2_f32
+};
+
+static Plan make_plan(const Shape &s, int cus)
+{
+    Plan p;
+    p.units = s.units;
+    const int cap = g_winograd_max_workgroups.load();
+    p.G = s.units < (unsigned)cus ? s.units : (unsigned)cus;
+    if (cap > 0 && p.G > (unsigned)cap) p.G = (unsigned)cap;
+    p.R = s.units / p.G;
+    p.rem = s.units % p.G;
+    const int tail = g_winograd_tail.load();
+    const bool on = p.rem > 0 && (tail == 2 || (tail == 1 && 2 * p.rem <= p.G && tail_family(s.C, s.K, s.d)));
+    p.half_units = on ? 2 * p.rem : 0;
+    const int v = g_winograd_variant.load();
+    p.variant = v ? v : variant2_family(s.C, s.K, s.d) ? 2 : 1;
+    return p;
 }
 
 // mode 0: the convolution alone (ep unread).  1..3: with the epilogue in the store.
@@ -567,21 +1218,7 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     }
     if (N == 0) return 0;
     Shape s;
-    s.N = N; s.H = H; s.W = W; s.C = C; s.K = K; s.d = dilation;
-    // every sub-lattice's own tile grid: th(sy) = (ceil((H - sy) / d) + 1) / 2 tile rows, none where H <= sy
-    s.py[0] = s.px[0] = 0;
-    for (int i = 0; i < 4; ++i) {
-        s.py[i + 1] = s.py[i] + (i < dilation && i < H ? ((H - i + dilation - 1) / dilation + 1) / 2 : 0);
-        s.px[i + 1] = s.px[i] + (i < dilation && i < W ? ((W - i + dilation - 1) / dilation + 1) / 2 : 0);
-    }
-    s.TY = s.py[4];
-    s.TX = s.px[4];
-    const int64_t tiles = (int64_t)N * s.TY * s.TX;
-    s.kblocks = K / KB;
-    const int64_t blocks = (tiles + TILES - 1) / TILES * s.kblocks;
-    if (tiles >= (int64_t)1 << 31 || blocks >= (int64_t)1 << 31) return (int)hipErrorNotSupported;
-    s.tiles = (unsigned)tiles;
-    s.units = (unsigned)blocks;
+    if (!tile_shape(s, N, H, W, C, K, dilation)) return (int)hipErrorNotSupported;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // the persistent grid: one workgroup per CU (one fits), each running every G-th unit; fewer under the tests' cap
     static PerDevice<int> cus_of;
@@ -591,9 +1228,9 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
             n = 256;
         return n;
     });
-    const int cap = g_winograd_max_workgroups.load();
-    unsigned nb = s.units < (unsigned)cus ? s.units : (unsigned)cus;
-    if (cap > 0 && nb > (unsigned)cap) nb = (unsigned)cap;
+    const Plan pl = make_plan(s, cus);
+    const unsigned nb = pl.G;
+    if (pl.half_units) s.units = pl.R * pl.G;                                 // what the persistent kernel runs; the tail starts there
     // the stride from a workgroup's unit to its next one (nb units on), over the tile grid
     s.gr = (int)(nb % (unsigned)s.kblocks);
     const auto stride = [&](int64_t tile_blocks, int &dX, int &dY, int &dn) {
@@ -604,12 +1241,15 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     };
     stride(nb / (unsigned)s.kblocks, s.dX0, s.dY0, s.dn0);
     stride(nb / (unsigned)s.kblocks + 1, s.dX1, s.dY1, s.dn1);
+    const unsigned tu = pl.half_units / 2;
     int rc;
-    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep);
-    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep) : launch<1, false>(st, nb, x, U, y, s, ep);
-    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep) : launch<2, false>(st, nb, x, U, y, s, ep);
-    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep) : launch<3, false>(st, nb, x, U, y, s, ep);
+    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
+    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<1, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
+    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<2, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
+    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<3, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
     if (rc != 0) return rc;
+    g_winograd_last_tail_units = (int)tu;
+    g_winograd_last_variant = pl.variant;
     g_winograd_last_kernel = "conv3x3_winograd_f32";
     g_winograd_last_epilogue = kEpilogueNames[mode][mode && relu ? 1 : 0];
     g_winograd_launches.fetch_add(1);
@@ -658,3 +1298,24 @@ extern "C" const char *mvdetr_winograd_last_epilogue(void) { return mvdetr::g_wi
 extern "C" int64_t mvdetr_winograd_launch_count(void) { return mvdetr::g_winograd_launches.load(); }
 
 extern "C" int mvdetr_winograd_set_max_workgroups(int n) { return mvdetr::g_winograd_max_workgroups.exchange(n > 0 ? n : 0); }
+
+extern "C" int mvdetr_winograd_set_tail(int mode) { return mvdetr::g_winograd_tail.exchange(mode == 0 || mode == 2 ? mode : 1); }
+
+extern "C" int mvdetr_winograd_set_variant(int v) { return mvdetr::g_winograd_variant.exchange(v == 1 || v == 2 ? v : 0); }
+
+extern "C" int mvdetr_winograd_last_variant(void) { return mvdetr::g_winograd_last_variant.load(); }
+
+extern "C" int mvdetr_winograd_last_tail_units(void) { return mvdetr::g_winograd_last_tail_units.load(); }
+
+extern "C" int mvdetr_winograd_plan(int N, int H, int W, int C, int K, int dilation, int workgroups, int64_t *out)
+{
+    using namespace mvdetr;
+    if (!out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || workgroups <= 0) return (int)hipErrorInvalidValue;
+    wino::Shape s;
+    if (C % 8 != 0 || K % 64 != 0 || !(dilation == 1 || dilation == 2 || dilation == 4) ||
+        !wino::tile_shape(s, N, H, W, C, K, dilation))
+        return (int)hipErrorNotSupported;
+    const wino::Plan p = wino::make_plan(s, workgroups);
+    out[0] = p.units; out[1] = p.G; out[2] = p.R; out[3] = p.rem; out[4] = p.half_units; out[5] = p.variant;
+    return 0;
+}

@@ -120,6 +120,47 @@ def set_winograd_max_workgroups(n: int) -> int:
     return int(_lib.lib().mvdetr_winograd_set_max_workgroups(int(n)))
 
 
+# (C, K, dilation) whose last round runs as half units under the default tail mode: the C library's table (tail_family in
+# csrc/conv_winograd.hip; tests/test_conv_winograd_plan.py holds the two together), by the family rule on
+# tools/conv_bench.py --tail (profiles/conv_winograd_w16_shapes.txt)
+TAIL_FAMILIES = ((64, 64, 1), (128, 128, 1), (128, 256, 1), (256, 256, 1), (256, 256, 2), (512, 512, 1))
+
+
+def set_winograd_tail(mode: int) -> int:
+    """How a convolution's last, partly empty round runs: 0 as whole units in the persistent kernel; 1 (the default) as
+    half units in a second launch where at most half the workgroups would be busy, on the shapes that measured faster
+    that way; 2 as half units whenever there is a remainder (tests).  Returns the previous mode; the bits of the result
+    do not depend on it."""
+    return int(_lib.lib().mvdetr_winograd_set_tail(int(mode)))
+
+
+def set_winograd_variant(variant: int) -> int:
+    """Which persistent kernel runs a convolution's whole units: 0 (the default) the one the C library's table names for the
+    (C, K, dilation); 1 conv3x3_winograd_f32 (4 waves, 32-channel wave blocks); 2 conv3x3_winograd_w16x2_f32 (8 waves,
+    16-channel wave blocks, two waves per SIMD).  Returns the previous setting; the bits of the result do not depend on it."""
+    return int(_lib.lib().mvdetr_winograd_set_variant(int(variant)))
+
+
+def last_variant() -> int:
+    """The persistent kernel of the last Winograd convolution: 1 or 2 (0 before the first)."""
+    return int(_lib.lib().mvdetr_winograd_last_variant())
+
+
+def last_tail_units() -> int:
+    """The units the last Winograd convolution ran as half units (0: it had no second launch)."""
+    return int(_lib.lib().mvdetr_winograd_last_tail_units())
+
+
+def plan(N: int, H: int, W: int, C: int, K: int, dilation: int, workgroups: int) -> dict:
+    """How a convolution call on ``workgroups`` CUs is split, under the current cap and tail mode, without a device:
+    units, G (the persistent grid), R = units // G, rem = units % G, the half units of the second launch and the variant."""
+    import ctypes
+    out = (ctypes.c_int64 * 6)()
+    _lib.check(_lib.lib().mvdetr_winograd_plan(N, H, W, C, K, dilation, workgroups, ctypes.cast(out, ctypes.c_void_p)),
+               "winograd_plan")
+    return dict(zip(("units", "G", "R", "rem", "half_units", "variant"), (int(v) for v in out)))
+
+
 def _on_device(t) -> bool:
     return t.is_cuda
 

@@ -5,6 +5,8 @@ MFMA kernel, interleaved in one process, HIP events.
 
     python tools/conv_bench.py [--reps 5] [--launches 20] [--out profiles/trunk_winograd_shapes.txt]
     python tools/conv_bench.py --epilogue [--out profiles/conv_winograd_epilogue_shapes.txt]
+    python tools/conv_bench.py --tail [--out profiles/conv_winograd_w16_shapes.txt]
+    python tools/conv_bench.py --variant
 
 A repetition times `launches` back-to-back launches of one side, then of the other; a family is switched on in
 mvdetr_amd/ops/conv_winograd.py only where the kernel is faster in EVERY repetition.  Also prints each shape's deviation
@@ -13,7 +15,15 @@ from an fp64 convolution for both sides (max-abs, on a post-ReLU N(0,1) input an
 --epilogue times the convolution WITH the block's epilogue, for every epilogue the trunk runs behind each shape, three sides
 interleaved: (a) torch's convolution + bn_act in place, (b) the plain Winograd kernel + bn_act in place, (c) the Winograd
 kernel with the epilogue in its store.  Besides the six layer3/4 shapes it times the two layer1/2 candidates at their own
-sizes; the same rule decides about them: (c) faster than (a) in every repetition, for every epilogue."""
+sizes; the same rule decides about them: (c) faster than (a) in every repetition, for every epilogue.
+
+--tail times the Winograd kernel against itself on the eight shapes, plain and with the first epilogue of each shape in its
+store: the last round as whole units in the persistent kernel (tail mode 0) against half units in a second launch (mode 2),
+interleaved.  A shape's tail is switched on (tail_family in csrc/conv_winograd.hip) only where mode 2 is faster in every
+repetition of every process run, on both rows.
+
+--variant times the 4-wave persistent kernel (variant 1) against the 8-wave one on 16-channel wave blocks (variant 2) the same
+way; the same rule fills variant2_family."""
 import argparse
 import os
 import sys
@@ -98,6 +108,100 @@ def epilogue_table(args, dev):
     return lines
 
 
+def tail_table(args, dev):
+    from mvdetr_amd.ops import conv_winograd as cw
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    lines = [f"# conv3x3_winograd_f32, last round as whole units (tail 0) vs as half units in a second launch (tail 2), fp32 "
+             f"channel-last, ms per convolution over {args.launches} launches, {args.reps} interleaved repetitions, {cus} CUs; "
+             "h = the half-unit launch's time in unit times, from the two medians and the fit (see --help)",
+             "# shape               C->K     d  pixels       store           units   R  rem   tail 0 min/med/max       "
+             "tail 2 min/med/max       wins   gain us   equal"]
+    for name, C, K, d, modes, pixels in EPILOGUE_SHAPES:
+        N, H, W = pixels or args.pixels
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last).eval()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        bn, bn2 = _bn(K, dev), _bn(K, dev)
+        res = torch.randn(N, K, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+        cw.set_winograd_tail(2)
+        p = cw.plan(N, H, W, C, K, d, cus)
+        for mode in ("none", modes[0]):
+            r, rbn = (None if mode in ("none", "bn") else res), (bn2 if mode == "bn_bn_add" else None)
+            if mode == "none":
+                fn = lambda: cw.winograd_conv3x3(x, conv, force=True)  # noqa: E731
+            else:
+                fn = lambda: cw.winograd_conv3x3_bn_act(x, conv, bn, r, rbn, relu=True, force=True)  # noqa: E731
+            t = [[], []]
+            with torch.no_grad():
+                outs = []
+                for tail in (0, 2):
+                    cw.set_winograd_tail(tail)
+                    for _ in range(3):
+                        y = fn()
+                    outs.append(y)
+                same = torch.equal(*outs)
+                for _ in range(args.reps):
+                    for side, tail in zip(t, (0, 2)):
+                        cw.set_winograd_tail(tail)
+                        side.append(timed(fn, args.launches))
+            cw.set_winograd_tail(1)
+            cols = "     ".join(f"{min(v):6.3f} {med(v):6.3f} {max(v):6.3f}" for v in t)
+            lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {(mode + '_relu') if mode != 'none' else 'plain':<15} "
+                         f"{p['units']:>5} {p['R']:>3} {p['rem']:>4}   {cols}     {sum(b < a for a, b in zip(*t))}/{args.reps}   "
+                         f"{(med(t[0]) - med(t[1])) * 1e3:7.1f}   {same}")
+            print(lines[-1], flush=True)
+    return lines
+
+
+def variant_table(args, dev):
+    """--variant: the 4-wave persistent kernel (variant 1) against the 8-wave one (variant 2), the tail in its default mode on
+    both sides, plain store and the shape's first fused store, interleaved."""
+    from mvdetr_amd.ops import conv_winograd as cw
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    lines = [f"# conv3x3_winograd_f32 (variant 1: 4 waves, 32-channel wave blocks) vs conv3x3_winograd_w16x2_f32 (variant 2: 8 waves, "
+             f"16-channel wave blocks), default tail on both, fp32 channel-last, ms per convolution over {args.launches} launches, "
+             f"{args.reps} interleaved repetitions",
+             "# shape               C->K     d  pixels       store           variant 1 min/med/max    variant 2 min/med/max    "
+             "wins   gain us   equal"]
+    for name, C, K, d, modes, pixels in EPILOGUE_SHAPES:
+        N, H, W = pixels or args.pixels
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last).eval()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        bn, bn2 = _bn(K, dev), _bn(K, dev)
+        res = torch.randn(N, K, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+        for mode in ("none", modes[0]):
+            r, rbn = (None if mode in ("none", "bn") else res), (bn2 if mode == "bn_bn_add" else None)
+            if mode == "none":
+                fn = lambda: cw.winograd_conv3x3(x, conv, force=True)  # noqa: E731
+            else:
+                fn = lambda: cw.winograd_conv3x3_bn_act(x, conv, bn, r, rbn, relu=True, force=True)  # noqa: E731
+            t = [[], []]
+            with torch.no_grad():
+                outs = []
+                for variant in (1, 2):
+                    cw.set_winograd_variant(variant)
+                    for _ in range(3):
+                        y = fn()
+                    outs.append(y)
+                same = torch.equal(*outs)
+                for _ in range(args.reps):
+                    for side, variant in zip(t, (1, 2)):
+                        cw.set_winograd_variant(variant)
+                        side.append(timed(fn, args.launches))
+            cw.set_winograd_variant(0)
+            cols = "     ".join(f"{min(v):6.3f} {med(v):6.3f} {max(v):6.3f}" for v in t)
+            lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {(mode + '_relu') if mode != 'none' else 'plain':<15} "
+                         f"{cols}     {sum(b < a for a, b in zip(*t))}/{args.reps}   {(med(t[0]) - med(t[1])) * 1e3:7.1f}   {same}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -105,6 +209,8 @@ def main():
     ap.add_argument("--pixels", type=int, nargs=3, default=(7, 90, 160), metavar=("N", "H", "W"))
     ap.add_argument("--out")
     ap.add_argument("--epilogue", action="store_true", help="time the convolutions with their epilogues, three sides")
+    ap.add_argument("--tail", action="store_true", help="time the last round as whole units against half units")
+    ap.add_argument("--variant", action="store_true", help="time the 4-wave persistent kernel against the 8-wave one")
     args = ap.parse_args()
     from mvdetr_amd.ops import conv_winograd as cw
     torch.backends.cudnn.benchmark = True
@@ -113,6 +219,10 @@ def main():
     shapes = SHAPES
     if args.epilogue:
         lines, shapes = epilogue_table(args, dev), []
+    elif args.tail:
+        lines, shapes = tail_table(args, dev), []
+    elif args.variant:
+        lines, shapes = variant_table(args, dev), []
     else:
         lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, fp32 channel-last, ms per launch "
                  f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",
