@@ -431,6 +431,43 @@ int mvdetr_winograd_set_tail(int mode);
 int mvdetr_winograd_last_tail_units(void);
 int mvdetr_winograd_plan(int N, int H, int W, int C, int K, int dilation, int workgroups, int64_t *out);
 
+/* ---- The backward of that convolution (csrc/conv_winograd_backward.hip; additive entries, the ABI version above is unchanged)
+ * Data gradient: for stride 1 and padding = dilation it is the same convolution of grad_y [N, H, W, K] with the weights
+ * flipped in both spatial axes and transposed in (C, K), so it needs one weight transform and no kernel of its own:
+ *   mvdetr_winograd_weights_dgrad_f32   w [K, C, 3, 3] dense -> Ut [16, K, C]: G g' G^T of g'[i][j] = w[k][c][2 - i][2 - j],
+ *                                       formed in fp64 and rounded once as mvdetr_winograd_weights_f32 does.  Feed it to
+ *                                       mvdetr_conv3x3_winograd_f32(grad_y, Ut, grad_x, N, H, W, K, C, ...), C and K
+ *                                       exchanged: C % 64 == 0 and K % 8 == 0 here.  Kernel name "winograd_weights_dgrad_f32".
+ * Weight gradient, in the Winograd domain: dU[p][c][k] = sum over the 2x2 tiles of (B^T d B)[p][tile][c] (A dY A^T)[p][tile][k],
+ * gw = G^T dU G -- sixteen GEMMs reduced over the forward's tile grid on v_mfma_f32_32x32x2_f32, 16 multiplications per
+ * (tile, c, k) against 36 of the direct form:
+ *   mvdetr_conv3x3_winograd_wgrad_f32   x [N, H, W, C], gy [N, H, W, K] (NHWC memory, only read) -> gw [K, C, 3, 3] dense,
+ *                                       every element written, nothing outside it.  A unit is a 64 x 64 block of (k, c); its
+ *                                       tiles are split over S workgroups, each with a contiguous range of chunks of 8 tiles,
+ *                                       whose partial gw go to slice s of `workspace` ([S, K, C, 3, 3] floats), and a second
+ *                                       small kernel sums the S slices in index order.  No atomics: for a given S the result
+ *                                       is bit-identical from call to call.  The library allocates nothing:
+ *   mvdetr_winograd_wgrad_workspace_bytes  what `workspace` must hold for a call on a device of `workgroups` CUs under the
+ *                                       current settings (-1 for a shape the call refuses)
+ *   mvdetr_winograd_wgrad_plan          without a device: out[5] = {units, chunks, S, chunks per split, chunks of the last
+ *                                       split}.  The default S is CUs / units (one workgroup per CU, which is what fits),
+ *                                       at least 1 and at most the chunks; mvdetr_winograd_set_max_workgroups caps the CUs
+ *                                       counted and the grid (the items (unit, split) then go round-robin).
+ *   mvdetr_winograd_set_wgrad_splits    force S (0: the default; clamped to the chunks); returns the previous setting.  Tests.
+ *   mvdetr_winograd_last_wgrad_splits   the S of the last weight-gradient call
+ * Contract of the weight gradient: C % 64 == 0, K % 64 == 0, dilation 1, 2 or 4, 16-byte aligned x, gy, gw, workspace, the
+ * forward's bounds ((256 + 2 H W) max(C, K) < 2^30, C K < 2^26, fewer than 2^31 tiles) and workspace_bytes at least what
+ * mvdetr_winograd_wgrad_workspace_bytes says: hipErrorNotSupported (801) otherwise; hipErrorInvalidValue for null x, gy, gw,
+ * sizes <= 0, and a gw or workspace whose bytes overlap an input's (or each other's).  N == 0 writes zeros to gw.
+ * One call is one count of mvdetr_winograd_launch_count, the reduce kernel included; its name is "conv3x3_winograd_wgrad_f32". */
+int mvdetr_winograd_weights_dgrad_f32(const float *w, int C, int K, float *Ut, void *stream);
+int mvdetr_conv3x3_winograd_wgrad_f32(const float *x, const float *gy, float *gw, int N, int H, int W, int C, int K, int dilation,
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mvdetr_winograd_wgrad_workspace_bytes(int N, int H, int W, int C, int K, int dilation, int workgroups);
+int mvdetr_winograd_wgrad_plan(int N, int H, int W, int C, int K, int dilation, int workgroups, int64_t *out);
+int mvdetr_winograd_set_wgrad_splits(int n);
+int mvdetr_winograd_last_wgrad_splits(void);
+
 /* ---- Introspection (used by bench.py / tests, not by the model code) ---------------------------
  * Name of the kernel variant the last forward call ON THIS THREAD dispatched to
  * ("gather", "tile16", ...).  Static storage; never NULL. */

@@ -115,6 +115,12 @@ SIGNATURES = {
     "mvdetr_winograd_last_variant": ([], _i),
     "mvdetr_winograd_last_tail_units": ([], _i),
     "mvdetr_winograd_plan": ([_i] * 7 + [_vp], _i),
+    "mvdetr_winograd_weights_dgrad_f32": ([_vp, _i, _i, _vp, _vp], _i),
+    "mvdetr_conv3x3_winograd_wgrad_f32": ([_vp] * 3 + [_i] * 6 + [_vp, ctypes.c_int64, _vp], _i),
+    "mvdetr_winograd_wgrad_workspace_bytes": ([_i] * 7, ctypes.c_int64),
+    "mvdetr_winograd_wgrad_plan": ([_i] * 7 + [_vp], _i),
+    "mvdetr_winograd_set_wgrad_splits": ([_i], _i),
+    "mvdetr_winograd_last_wgrad_splits": ([], _i),
     "mvdetr_warp_perspective_forward_f32": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f64": (_WARP, _i),
     "mvdetr_warp_perspective_forward_f16": (_WARP, _i),

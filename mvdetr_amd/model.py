@@ -20,7 +20,8 @@ from torch import nn
 from . import geometry
 from .ops import warp_perspective
 from .ops.conv_winograd import (winograd_conv3x3, winograd_conv3x3_available, winograd_conv3x3_bn_act,
-                                winograd_conv3x3_bn_act_available)
+                                winograd_conv3x3_bn_act_available, winograd_conv3x3_train,
+                                winograd_conv3x3_train_available)
 from .ops.detect import bev_detect
 from .ops.peak_detect import peak_detect, PeakDetections
 from .ops.ingest import ingest_frames
@@ -42,9 +43,11 @@ def _fused_bn_act(out, bn, residual=None, residual_bn=None):
 
 def _conv3x3(x, conv):
     """conv(x): the fp32 Winograd kernel where it takes these arguments (inference, wide 3x3 convolutions at the trunk's
-    size), torch's convolution otherwise."""
+    size; under autograd its differentiable form, on the families of TRAIN_FAMILIES), torch's convolution otherwise."""
     if winograd_conv3x3_available(x, conv):
         return winograd_conv3x3(x, conv)
+    if winograd_conv3x3_train_available(x, conv):
+        return winograd_conv3x3_train(x, conv)
     return conv(x)
 
 

@@ -7,6 +7,7 @@ MFMA kernel, interleaved in one process, HIP events.
     python tools/conv_bench.py --epilogue [--out profiles/conv_winograd_epilogue_shapes.txt]
     python tools/conv_bench.py --tail [--out profiles/conv_winograd_w16_shapes.txt]
     python tools/conv_bench.py --variant
+    python tools/conv_bench.py --backward [--out profiles/conv_winograd_backward_shapes.txt]
 
 A repetition times `launches` back-to-back launches of one side, then of the other; a family is switched on in
 mvdetr_amd/ops/conv_winograd.py only where the kernel is faster in EVERY repetition.  Also prints each shape's deviation
@@ -23,7 +24,12 @@ interleaved.  A shape's tail is switched on (tail_family in csrc/conv_winograd.h
 repetition of every process run, on both rows.
 
 --variant times the 4-wave persistent kernel (variant 1) against the 8-wave one on 16-channel wave blocks (variant 2) the same
-way; the same rule fills variant2_family."""
+way; the same rule fills variant2_family.
+
+--backward times the training pieces on the eight shapes, each against torch's convolution_backward (cudnn.benchmark) with the
+matching output mask, interleaved: the data gradient alone (the forward kernel on Ut), the weight gradient alone
+(conv3x3_winograd_wgrad_f32 and its reduction), and forward + backward together through winograd_conv3x3_train against
+torch's conv + autograd.  A piece of a family goes into TRAIN_FAMILIES only where it is faster in every repetition."""
 import argparse
 import os
 import sys
@@ -202,6 +208,58 @@ def variant_table(args, dev):
     return lines
 
 
+def backward_table(args, dev):
+    """--backward: dgrad alone, wgrad alone, forward + backward together; Winograd against torch, interleaved."""
+    from mvdetr_amd.ops import conv_winograd as cw
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    lines = [f"# the training pieces of a 3x3 convolution, fp32 channel-last, ms over {args.launches} launches, {args.reps} interleaved "
+             f"repetitions, {cus} CUs: torch = aten.convolution_backward with the piece's output mask (MIOpen, cudnn.benchmark); "
+             "winograd = dgrad: conv3x3_winograd_f32 on Ut, wgrad: conv3x3_winograd_wgrad_f32 + its reduction (S splits), "
+             "fwd+bwd: winograd_conv3x3_train(force) + autograd against conv(x) + autograd, both gradients; err = max-abs "
+             "deviation from fp64 on the first image's worth of grad_x / on grad_w",
+             "# shape               C->K     d  pixels       piece     S   torch min/med/max        winograd min/med/max     "
+             "wins  err torch / winograd vs fp64"]
+    for name, C, K, d, pixels in SHAPES:
+        N, H, W = pixels or args.pixels
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last)
+        w = conv.weight.detach()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        gy = torch.randn(N, K, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+        xg = x.clone(memory_format=torch.preserve_format).requires_grad_(True)
+        back = lambda mask: torch.ops.aten.convolution_backward(gy, x, w, None, (1, 1), (d, d), (d, d), False, (0, 0), 1, mask)  # noqa: E731
+        sides = {
+            "dgrad": (lambda: back([True, False, False])[0], lambda: cw.winograd_conv3x3_input_grad(gy, w, d)),
+            "wgrad": (lambda: back([False, True, False])[1], lambda: cw.winograd_conv3x3_weight_grad(x, gy, d)),
+            "fwd+bwd": (lambda: torch.autograd.grad(conv(xg), (xg, conv.weight), gy),
+                        lambda: torch.autograd.grad(cw.winograd_conv3x3_train(xg, conv, force=True), (xg, conv.weight), gy)),
+        }
+        S = cw.wgrad_plan(N, H, W, C, K, d, cus)["S"]
+        want_x = torch.nn.grad.conv2d_input((1, C, H, W), w.double(), gy[:1].double(), 1, d, d)
+        want_w = torch.nn.grad.conv2d_weight(x.double(), w.shape, gy.double(), 1, d, d)
+        for piece, (torch_side, wino_side) in sides.items():
+            for _ in range(3):
+                ref, got = torch_side(), wino_side()
+            if piece == "dgrad":
+                err = f"{(ref[:1] - want_x).abs().max().item():.2e} / {(got[:1] - want_x).abs().max().item():.2e}"
+            elif piece == "wgrad":
+                err = f"{(ref - want_w).abs().max().item():.2e} / {(got - want_w).abs().max().item():.2e}"
+            else:
+                err = "-"
+            t_t, t_w = [], []
+            for _ in range(args.reps):
+                t_t.append(timed(torch_side, args.launches))
+                t_w.append(timed(wino_side, args.launches))
+            wins = sum(a < b for a, b in zip(t_w, t_t))
+            lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {piece:<8} {S:>3}   {min(t_t):6.3f} {med(t_t):6.3f} {max(t_t):6.3f}     "
+                         f"{min(t_w):6.3f} {med(t_w):6.3f} {max(t_w):6.3f}     {wins}/{args.reps}   {err}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -211,6 +269,7 @@ def main():
     ap.add_argument("--epilogue", action="store_true", help="time the convolutions with their epilogues, three sides")
     ap.add_argument("--tail", action="store_true", help="time the last round as whole units against half units")
     ap.add_argument("--variant", action="store_true", help="time the 4-wave persistent kernel against the 8-wave one")
+    ap.add_argument("--backward", action="store_true", help="time the data gradient, the weight gradient and forward + backward")
     args = ap.parse_args()
     from mvdetr_amd.ops import conv_winograd as cw
     torch.backends.cudnn.benchmark = True
@@ -223,6 +282,8 @@ def main():
         lines, shapes = tail_table(args, dev), []
     elif args.variant:
         lines, shapes = variant_table(args, dev), []
+    elif args.backward:
+        lines, shapes = backward_table(args, dev), []
     else:
         lines = [f"# torch (MIOpen, cudnn.benchmark) vs conv3x3_winograd_f32, fp32 channel-last, ms per launch "
                  f"over {args.launches} launches, {args.reps} interleaved repetitions; GFLOP = direct form",

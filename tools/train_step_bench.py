@@ -6,6 +6,13 @@ against the torch composition of the same formulas (the loss switch off), altern
   step        one whole Wildtrack training step: train_step with Adam, fp32, deform_trans, the switch on and off.
 
     python tools/train_step_bench.py [--reps N] [--skip-step]
+    python tools/train_step_bench.py --winograd-train [--families shipped|all] [--out profiles/trunk_winograd_train_ab.txt]
+
+--winograd-train times the same whole step with the trunk's Winograd training convolutions on and off
+(set_trunk_winograd_training), alternated in one process, and counts the Winograd launches of a step on either side: with
+the switch off there are none, so that side runs the launches of the code without the route.  ``--families all`` switches every
+3x3 convolution the route can take on with both pieces (a measurement of the route as a whole; the shipped table is what
+tools/conv_bench.py --backward filled).
 
 Two clocks per repetition: device-event time between the first and the last enqueued kernel, and host wall time from the
 call to the end of a synchronise behind it.  A host synchronise in the middle of the composition costs queue idle time that
@@ -113,14 +120,68 @@ def bench_step(reps, rows):
     emit(rows, "train step (Adam, fp32, deform_trans)", "wildtrack", res)
 
 
+def bench_winograd_train(reps, families, out):
+    """The whole Wildtrack step with the Winograd training route on against off, alternated; a table to ``out``."""
+    from torch import nn
+    from mvdetr_amd.ops import conv_winograd as cw
+    geom = geometry.WILDTRACK
+    model = build_model("wildtrack", seed=0, world_feat_arch="deform_trans", channels_last=True).to(DEV).train()
+    if families == "all":
+        for m in model.modules():
+            if (type(m) is nn.Conv2d and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == m.dilation and m.bias is None
+                    and m.in_channels % 64 == 0 and m.out_channels % 64 == 0 and m.dilation[0] in cw.DILATIONS):
+                cw.TRAIN_FAMILIES.setdefault((m.in_channels, m.out_channels), {})[m.dilation[0]] = cw.PIECES
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    world_gt, imgs_gt = synthetic_frame_targets(geom, PEOPLE, seed=0)
+    world_gt, imgs_gt = ({k: v.to(DEV) for k, v in d.items()} for d in (world_gt, imgs_gt))
+    imgs = torch.randn(1, geom.num_cam, 3, *geom.input_img_shape, generator=torch.Generator().manual_seed(1)).to(DEV)
+    M = torch.eye(3).repeat(1, geom.num_cam, 1, 1)
+    crit = MVDeTrCriterion()
+    launches = {}
+
+    def side(name, on):
+        def run():
+            prev = cw.set_trunk_winograd_training(on)
+            n0 = cw.launch_count()
+            try:
+                return train_step(model, crit, opt, imgs, M, world_gt, imgs_gt)
+            finally:
+                launches[name] = cw.launch_count() - n0
+                cw.set_trunk_winograd_training(prev)
+        return run
+
+    res = alternated({"on": side("on", True), "off": side("off", False)}, reps, warmup=2)
+    table = {f"{C}->{K} d {d}": "+".join(p) for (C, K), ds in sorted(cw.TRAIN_FAMILIES.items()) for d, p in sorted(ds.items()) if p}
+    lines = [f"# one Wildtrack training step (train_step, Adam, fp32, deform_trans), set_trunk_winograd_training on against off, "
+             f"alternated in one process; {torch.cuda.get_device_name(0)}; torch {torch.__version__}; median of {reps} (min .. max), ms",
+             f"# TRAIN_FAMILIES ({families}): {table if table else 'empty -- both sides run the same launches'}",
+             f"# Winograd launches in a step: on {launches['on']}, off {launches['off']} (off: none -- the launches of the code without the route)"]
+    for clock in ("device", "wall"):
+        for name in ("on", "off"):
+            med, lo, hi = res[name][clock]
+            lines.append(f"{clock:<7} {name:<4} {med / 1e3:9.3f}  ({lo / 1e3:.3f} .. {hi / 1e3:.3f})")
+        lines.append(f"{clock:<7} off - on = {(res['off'][clock][0] - res['on'][clock][0]) / 1e3:+.3f} ms")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--winograd-train", action="store_true", help="A/B of the trunk's Winograd training convolutions on the whole step")
+    ap.add_argument("--families", choices=("shipped", "all"), default="shipped")
+    ap.add_argument("--out")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_step_bench: needs a GPU (no CPU fallback for timings)")
     reps = max(20, a.reps)
+    if a.winograd_train:
+        return bench_winograd_train(reps, a.families, a.out)
     print(f"# device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; median of {reps} alternated repetitions (min .. max)")
     rows = []
     for name in ("wildtrack", "multiviewx"):
