@@ -430,6 +430,18 @@ int mvdetr_winograd_last_variant(void);
 int mvdetr_winograd_set_tail(int mode);
 int mvdetr_winograd_last_tail_units(void);
 int mvdetr_winograd_plan(int N, int H, int W, int C, int K, int dilation, int workgroups, int64_t *out);
+/* How form 2 deals a chunk's memory work to the two waves of a SIMD (additive entries, the ABI version above is unchanged;
+ * the plan's six fields do not depend on it).  Schedule 1, lockstep: all eight waves run one program, so both waves of a SIMD
+ * issue their loads in the same half k-step.  Schedule 2, de-phased: waves 4-7 run a program of their own with the same
+ * arithmetic, barrier and LDS layout, whose loads and input transform sit in other half k-steps.  The same bits.
+ *   mvdetr_winograd_set_schedule     0: the default -- 2 on the (C, K, dilation) on which it measured faster, 1 elsewhere;
+ *                                    1 or 2: that one on every shape (tests, A/B); anything else is 0.  Returns the previous
+ *                                    setting.
+ *   mvdetr_winograd_last_schedule    the schedule of the last convolution call (0 before the first; 1 where it ran form 1)
+ *   mvdetr_winograd_schedule_of      what a form 2 launch of this (C, K, dilation) takes under the current setting: 1 or 2 */
+int mvdetr_winograd_set_schedule(int schedule);
+int mvdetr_winograd_last_schedule(void);
+int mvdetr_winograd_schedule_of(int C, int K, int dilation);
 
 /* ---- The backward of that convolution (csrc/conv_winograd_backward.hip; additive entries, the ABI version above is unchanged)
  * Data gradient: for stride 1 and padding = dilation it is the same convolution of grad_y [N, H, W, K] with the weights

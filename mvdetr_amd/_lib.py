@@ -114,6 +114,9 @@ SIGNATURES = {
     "mvdetr_winograd_set_variant": ([_i], _i),
     "mvdetr_winograd_last_variant": ([], _i),
     "mvdetr_winograd_last_tail_units": ([], _i),
+    "mvdetr_winograd_set_schedule": ([_i], _i),
+    "mvdetr_winograd_last_schedule": ([], _i),
+    "mvdetr_winograd_schedule_of": ([_i] * 3, _i),
     "mvdetr_winograd_plan": ([_i] * 7 + [_vp], _i),
     "mvdetr_winograd_weights_dgrad_f32": ([_vp, _i, _i, _vp, _vp], _i),
     "mvdetr_conv3x3_winograd_wgrad_f32": ([_vp] * 3 + [_i] * 6 + [_vp, ctypes.c_int64, _vp], _i),

@@ -59,6 +59,8 @@ static std::atomic<int> g_winograd_tail{1};                                   //
 static std::atomic<int> g_winograd_last_tail_units{0};
 static std::atomic<int> g_winograd_variant{0};                                // mvdetr_winograd_set_variant
 static std::atomic<int> g_winograd_last_variant{0};
+static std::atomic<int> g_winograd_schedule{0};                               // mvdetr_winograd_set_schedule
+static std::atomic<int> g_winograd_last_schedule{0};
 
 namespace wino {
 
@@ -717,16 +719,38 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_w16_f32(const float *__r
 //   barrier
 //   k-step 1, positions 8-15    the x loads of the chunk after next, the reads of the next chunk's first set, the LDS-DMA of U
 // The loader has one (tile, channel) per lane as in the half-unit kernel; V keeps 72 columns, U is 4 LDS-DMA per lane.
-template <int MODE, bool RELU>
-__global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *__restrict__ x, const float *__restrict__ U,
-                                                                  float *__restrict__ y, const Shape s, const Epilogue ep)
+//
+// That is DEAL 0, and under schedule 1 (lockstep) all eight waves run it: both waves of a SIMD issue their sixteen x loads and
+// four LDS-DMA in the same half k-step.  The memory work of a chunk may sit elsewhere without another barrier, LDS buffer or
+// bit of the result: with c the chunk a wave computes, buf[c & 1] its operands' buffer and the barrier of c between its third
+// and fourth half k-step (h0 .. h3),
+//   V of chunk c + 1   -> buf[(c + 1) & 1], last read before the barrier of c - 1, first read in h3(c): anywhere in h3(c - 1) .. h2(c)
+//   U of chunk c + 2   -> buf[c & 1], last read before the barrier of c, first read in h3(c + 1): issued in h3(c) .. h1(c + 1), under
+//                         the vmcnt(0) before the barrier of c + 1
+//   x of chunk c + 2   -> raw[], once the transform of chunk c + 1 has read it, landed by the transform's first piece
+// DEAL 1 (early) is the program of waves 4-7 under schedule 2 (de-phased; waves 0-3 keep deal 0), at priority 1:
+//   h0(c)   the reads; U of chunk c + 1, under the staging cursor of before this chunk's advance(); the second half of the
+//           transform of chunk c + 1
+//   h1(c)   the reads; the x loads of chunk c + 2
+//   h2(c)   the reads
+//   barrier
+//   h3(c)   eight bare MFMAs beside the other role's loads, then the reads and the first half of the transform of chunk c + 2
+// Both deals have the same barrier statement, once per chunk, and the same trip counts, so every wave arrives at every barrier.
+// The whole kernel under one deal.  A role's program is a copy of ALL of it, setup included, behind the kernel's one branch
+// (ROLES: this is one of two copies), so that no vector register is live across the other role's loop: not the thread index
+// either, which a copy takes from its wave's number and the lane count, in a statement of its own that cannot be hoisted.
+template <int MODE, bool RELU, int DEAL, bool ROLES>
+__device__ __forceinline__ void conv3x3_winograd_w16x2_deal(const float *__restrict__ x, const float *__restrict__ U,
+                                                            float *__restrict__ y, const Shape &s, const Epilogue &ep,
+                                                            const int wave)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int lane = threadIdx.x & 63;
+    if (ROLES) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0 ; deal %1" : "=v"(lane) : "n"(DEAL));
+    const int tid = wave * 64 + lane;
     const int C = s.C, K = s.K, d = s.d, H = s.H, W = s.W;
     const int chunks = C / CC;
     const unsigned G = gridDim.x;
@@ -868,8 +892,13 @@ __global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *_
         advance();
 #pragma unroll
         for (int q = 0; q < 16; ++q) load_x(sc * CC, q);
+        if (DEAL == 1) {                                                      // the first half of chunk 1's transform; its U in h0
 #pragma unroll
-        for (int r = 0; r < 4; ++r) load_u(sc * CC, lds + BUF_FLOATS, r);
+            for (int u = 0; u < 8; ++u) xform_piece(lds + BUF_FLOATS, u);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) load_u(sc * CC, lds + BUF_FLOATS, r);
+        }
 #pragma unroll
         for (int q = 0; q < 8; ++q) read_piece(lds, 0, q);
     }
@@ -879,8 +908,11 @@ __global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *_
     int kb_folded = -1;
     unsigned cu = blockIdx.x;
     int cslot = 0, par = 0;
-    auto chunk = [&](auto first) {
-        advance();
+    // One chunk under deal D (above).  Deal 0 moves the staging cursor at the top, to the chunk after next; deal 1 behind h0,
+    // whose LDS-DMA is still the next chunk's.
+    auto chunk = [&](auto first, auto deal) {
+        constexpr int D = decltype(deal)::value;
+        if (D == 0) advance();
         float *const cur = lds + par * BUF_FLOATS;
         float *const nxt = lds + (par ^ 1) * BUF_FLOATS;
         __builtin_amdgcn_sched_barrier(0);
@@ -888,20 +920,32 @@ __global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *_
         for (int m = 0; m < 16; ++m) {
             mfma(0, m, first);
             if (m < 8) read_piece(cur, 1, m);
+            if (D == 1 && m < 4) load_u(sc * CC, nxt, m);
+            if (D == 1 && m >= 8) xform_piece(nxt, m);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (D != 0) {
+            advance();
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             mfma(1, m, first);
-            if (m < 8) read_piece(cur, 2, m);
-            else xform_piece(nxt, m - 8);
+            if (m < 8) {
+                read_piece(cur, 2, m);
+            } else if (D == 1) {
+                load_x(sc * CC, 2 * (m - 8));
+                load_x(sc * CC, 2 * (m - 8) + 1);
+            } else {
+                xform_piece(nxt, m - 8);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             mfma(2, m, std::false_type{});
             if (m < 8) read_piece(cur, 3, m);
-            else xform_piece(nxt, m);
+            else if (D == 0) xform_piece(nxt, m);
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -909,109 +953,138 @@ __global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *_
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             mfma(3, m, std::false_type{});
-            if (m < 8) {
-                load_x(sc * CC, 2 * m);
-                load_x(sc * CC, 2 * m + 1);
-            } else {
+            if (D == 0) {
+                if (m < 8) {
+                    load_x(sc * CC, 2 * m);
+                    load_x(sc * CC, 2 * m + 1);
+                } else {
+                    read_piece(nxt, 0, m - 8);
+                    if (m < 12) load_u(sc * CC, cur, m - 8);
+                }
+            } else if (m >= 8) {                                              // bare MFMAs behind the barrier, beside the other role's loads
                 read_piece(nxt, 0, m - 8);
-                if (m < 12) load_u(sc * CC, cur, m - 8);
+                xform_piece(cur, m - 8);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         par ^= 1;
     };
-    do {
-        chunk(std::true_type{});
+    // the chunks of one unit: every deal has the same trips, and the barrier above is their one barrier statement
+    auto unit_chunks = [&](auto deal) {
+        chunk(std::true_type{}, deal);
         if (chunks > 1) {
             int ch = 1;
-            do chunk(std::false_type{});
+            do chunk(std::false_type{}, deal);
             while (++ch < chunks);
         }
+    };
+    // the units of this workgroup under one deal: a role runs its own copy of the whole loop, store included
+    auto units = [&](auto deal) {
+        do {
+            unit_chunks(deal);
 
-        // ---- the store: conv3x3_winograd_f32's, over 2 tile blocks x 4 registers ------------------------------------------------
-        const int kb = cpl.kb, n0 = cpl.n;
-        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
-        const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
-        const __amdgpu_buffer_rsrc_t yrsrc =
-            __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
-        // register r of tile block h is tile 32 (w / 4) + 16 h + 4 (lane >> 4) + r
-        const u32x4 *const ti = tinfo + cslot * TILES + th * 32 + 4 * (lane >> 4);
-        auto offsets = [&](int b, unsigned (&o4)[4]) {
-            const u32x4 dsc = ti[16 * (b >> 2) + (b & 3)];
+            // ---- the store: conv3x3_winograd_f32's, over 2 tile blocks x 4 registers ------------------------------------------------
+            const int kb = cpl.kb, n0 = cpl.n;
+            const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
+            const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
+            const __amdgpu_buffer_rsrc_t yrsrc =
+                __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+            // register r of tile block h is tile 32 (w / 4) + 16 h + 4 (lane >> 4) + r
+            const u32x4 *const ti = tinfo + cslot * TILES + th * 32 + 4 * (lane >> 4);
+            auto offsets = [&](int b, unsigned (&o4)[4]) {
+                const u32x4 dsc = ti[16 * (b >> 2) + (b & 3)];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
-        };
-        if (MODE >= 1 && kb != kb_folded) {
-            bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
-            if (MODE == 3) {
-                float bt2;
-                bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
-                bt = bt + bt2;
+                for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+            };
+            if (MODE >= 1 && kb != kb_folded) {
+                bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
+                if (MODE == 3) {
+                    float bt2;
+                    bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
+                    bt = bt + bt2;
+                }
+                kb_folded = kb;
             }
-            kb_folded = kb;
-        }
-        float q[2][4][4];                                                     // the residual of one tile block, one block ahead
-        __amdgpu_buffer_rsrc_t rrsrc;
-        if (MODE >= 2)
-            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
-                                                      0x00020000);
-        auto load_res = [&](int h) {
+            // the second block's residual: behind the first block's first row, or (a role copy with two BatchNorms, which has a
+            // register less) behind its third
+            constexpr int RES1_AT = ROLES && MODE == 3 ? 2 : 0;
+            float q[2][4][4];                                                     // the residual of one tile block, one block ahead
+            __amdgpu_buffer_rsrc_t rrsrc;
+            if (MODE >= 2)
+                rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
+                                                          0x00020000);
+            auto load_res = [&](int h) {
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                unsigned o4[4];
-                offsets(4 * h + rr, o4);
+                for (int rr = 0; rr < 4; ++rr) {
+                    unsigned o4[4];
+                    offsets(4 * h + rr, o4);
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    q[h][rr][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
-            }
-        };
-        if (MODE >= 2) {
-            load_res(0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // 18 wait states between the last MFMA's write and the hand-written reads of its registers (more than an 8-pass MFMA needs)
-        asm volatile("s_nop 15\n\ts_nop 3");
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const int h = b >> 2, r = b & 3;
-            if (MODE >= 2 && b == 0) {
-                load_res(1);
+                    for (int e = 0; e < 4; ++e)
+                        q[h][rr][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, (int)o4[e], 0, 0));
+                }
+            };
+            if (MODE >= 2) {
+                load_res(0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            unsigned o4[4];
-            offsets(b, o4);
-            float m[16];
+            // 18 wait states between the last MFMA's write and the hand-written reads of its registers (more than an 8-pass MFMA needs)
+            asm volatile("s_nop 15\n\ts_nop 3");
 #pragma unroll
-            for (int p = 0; p < 16; ++p) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[p]) : "a"(acc[p][h][r]));
-            float s0[4], s1[4];
+            for (int b = 0; b < 8; ++b) {
+                const int h = b >> 2, r = b & 3;
+                if (MODE >= 2 && b == RES1_AT) {
+                    load_res(1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                unsigned o4[4];
+                offsets(b, o4);
+                float m[16];
 #pragma unroll
-            for (int nu = 0; nu < 4; ++nu) {
-                s0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
-                s1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
+                for (int p = 0; p < 16; ++p) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[p]) : "a"(acc[p][h][r]));
+                float s0[4], s1[4];
+#pragma unroll
+                for (int nu = 0; nu < 4; ++nu) {
+                    s0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
+                    s1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
+                }
+                float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
+                float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
+                if (MODE >= 1) {
+                    constexpr int RES = MODE - 1;
+                    const float *const qr = q[h][r];
+                    y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? qr[0] : 0.f, bs2);
+                    y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? qr[1] : 0.f, bs2);
+                    y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? qr[2] : 0.f, bs2);
+                    y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? qr[3] : 0.f, bs2);
+                }
+                const float y4[4] = {y00, y01, y10, y11};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y4[e]), yrsrc, (int)o4[e], 0, 0);
+#pragma unroll
+                for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p][0]), "+a"(acc[p][1]));
+                __builtin_amdgcn_sched_barrier(0);
             }
-            float y00 = s0[0] + s0[1] + s0[2], y01 = s0[1] - s0[2] - s0[3];
-            float y10 = s1[0] + s1[1] + s1[2], y11 = s1[1] - s1[2] - s1[3];
-            if (MODE >= 1) {
-                constexpr int RES = MODE - 1;
-                const float *const qr = q[h][r];
-                y00 = bn_finish<RES, RELU>(bn_apply(y00, bs, bt), RES ? qr[0] : 0.f, bs2);
-                y01 = bn_finish<RES, RELU>(bn_apply(y01, bs, bt), RES ? qr[1] : 0.f, bs2);
-                y10 = bn_finish<RES, RELU>(bn_apply(y10, bs, bt), RES ? qr[2] : 0.f, bs2);
-                y11 = bn_finish<RES, RELU>(bn_apply(y11, bs, bt), RES ? qr[3] : 0.f, bs2);
-            }
-            const float y4[4] = {y00, y01, y10, y11};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y4[e]), yrsrc, (int)o4[e], 0, 0);
-#pragma unroll
-            for (int p = 0; p < 16; ++p) asm volatile("" : "+a"(acc[p][0]), "+a"(acc[p][1]));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        cu += G;
-        next_unit(cpl);
-        cslot = (cslot + 1) & (TINFO_SLOTS - 1);
-    } while (cu < s.units);
+            cu += G;
+            next_unit(cpl);
+            cslot = (cslot + 1) & (TINFO_SLOTS - 1);
+        } while (cu < s.units);
+    };
+    units(std::integral_constant<int, DEAL>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+template <int MODE, bool RELU, int SCHED>
+__global__ __launch_bounds__(512) void conv3x3_winograd_w16x2_f32(const float *__restrict__ x, const float *__restrict__ U,
+                                                                  float *__restrict__ y, const Shape s, const Epilogue ep)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (SCHED == 2 && wave >= 4) {                                            // wave-uniform: one scalar branch
+        __builtin_amdgcn_s_setprio(1);
+        conv3x3_winograd_w16x2_deal<MODE, RELU, 1, true>(x, U, y, s, ep, wave);
+    } else {
+        conv3x3_winograd_w16x2_deal<MODE, RELU, 0, SCHED == 2>(x, U, y, s, ep, wave);
+    }
 }
 
 // U[p = 4 xi + nu][c][k] = (G g G^T)[xi][nu] of weight[k][c][3][3], in fp64, rounded once.  One thread per (c, k).
@@ -1043,22 +1116,25 @@ __global__ __launch_bounds__(256) void winograd_weights_f32(const float *__restr
 // the half-unit kernel over the 2 * tail_units halves of the units behind them
 template <int MODE, bool RELU>
 static int launch(hipStream_t st, unsigned blocks, const float *x, const float *U, float *y, const Shape &s, const Epilogue &ep,
-                  int variant, unsigned tail_units)
+                  int variant, int schedule, unsigned tail_units)
 {
     static PerDevice<int> lds_attr;
     const int rc = lds_attr.get([] {
-        const void *const kernels[3] = {reinterpret_cast<const void *>(conv3x3_winograd_f32<MODE, RELU>),
-                                        reinterpret_cast<const void *>(conv3x3_winograd_w16x2_f32<MODE, RELU>),
-                                        reinterpret_cast<const void *>(conv3x3_winograd_w16_f32<MODE, RELU>)};
-        for (int i = 0; i < 3; ++i) {
-            const int a = (int)hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 2 ? LDS_BYTES : w16::LDS_BYTES);
+        const void *const kernels[4] = {reinterpret_cast<const void *>(conv3x3_winograd_w16_f32<MODE, RELU>),
+                                        reinterpret_cast<const void *>(conv3x3_winograd_f32<MODE, RELU>),
+                                        reinterpret_cast<const void *>(conv3x3_winograd_w16x2_f32<MODE, RELU, 1>),
+                                        reinterpret_cast<const void *>(conv3x3_winograd_w16x2_f32<MODE, RELU, 2>)};
+        for (int i = 0; i < 4; ++i) {
+            const int a = (int)hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, i ? LDS_BYTES : w16::LDS_BYTES);
             if (a != 0) return a;
         }
         return 0;
     });
     if (rc != 0) return rc;
-    if (variant == 2)
-        hipLaunchKernelGGL((conv3x3_winograd_w16x2_f32<MODE, RELU>), dim3(blocks), dim3(512), LDS_BYTES, st, x, U, y, s, ep);
+    if (variant == 2 && schedule == 2)
+        hipLaunchKernelGGL((conv3x3_winograd_w16x2_f32<MODE, RELU, 2>), dim3(blocks), dim3(512), LDS_BYTES, st, x, U, y, s, ep);
+    else if (variant == 2)
+        hipLaunchKernelGGL((conv3x3_winograd_w16x2_f32<MODE, RELU, 1>), dim3(blocks), dim3(512), LDS_BYTES, st, x, U, y, s, ep);
     else
         hipLaunchKernelGGL((conv3x3_winograd_f32<MODE, RELU>), dim3(blocks), dim3(256), LDS_BYTES, st, x, U, y, s, ep);
     if (tail_units)
@@ -1095,6 +1171,23 @@ static bool variant2_family(int C, int K, int d)
     for (const auto &f : table)
         if (f[0] == C && f[1] == K && f[2] == d) return true;
     return false;
+}
+
+// The (C, K, dilation) whose 8-wave launch runs the de-phased schedule under schedule mode 0: those on which it measured faster
+// than lockstep in every repetition of tools/conv_bench.py --schedule (profiles/conv_winograd_dephase_shapes.txt)
+static bool schedule_family(int C, int K, int d)
+{
+    static const int table[][3] = {{64, 64, 1}, {128, 128, 1}, {256, 256, 1}, {256, 256, 2}, {256, 512, 2}, {512, 512, 1}, {512, 512, 4}};
+    for (const auto &f : table)
+        if (f[0] == C && f[1] == K && f[2] == d) return true;
+    return false;
+}
+
+// The schedule of an 8-wave launch of this shape under the current mode: 1 lockstep, 2 de-phased
+static int schedule_of(int C, int K, int d)
+{
+    const int v = g_winograd_schedule.load();
+    return v ? v : schedule_family(C, K, d) ? 2 : 1;
 }
 
 // How a call is split: G persistent workgroups run the units [0, R G) and, where the rest is a tail, 2 rem half units run
@@ -1170,14 +1263,16 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     stride(nb / (unsigned)s.kblocks, s.dX0, s.dY0, s.dn0);
     stride(nb / (unsigned)s.kblocks + 1, s.dX1, s.dY1, s.dn1);
     const unsigned tu = pl.half_units / 2;
+    const int sch = pl.variant == 2 ? schedule_of(C, K, dilation) : 1;       // the 4-wave kernel has one program
     int rc;
-    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
-    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<1, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
-    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<2, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
-    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep, pl.variant, tu) : launch<3, false>(st, nb, x, U, y, s, ep, pl.variant, tu);
+    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
+    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<1, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
+    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<2, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
+    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<3, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
     if (rc != 0) return rc;
     g_winograd_last_tail_units = (int)tu;
     g_winograd_last_variant = pl.variant;
+    g_winograd_last_schedule = sch;
     g_winograd_last_kernel = "conv3x3_winograd_f32";
     g_winograd_last_epilogue = kEpilogueNames[mode][mode && relu ? 1 : 0];
     g_winograd_launches.fetch_add(1);
@@ -1232,6 +1327,12 @@ extern "C" int mvdetr_winograd_set_tail(int mode) { return mvdetr::g_winograd_ta
 extern "C" int mvdetr_winograd_set_variant(int v) { return mvdetr::g_winograd_variant.exchange(v == 1 || v == 2 ? v : 0); }
 
 extern "C" int mvdetr_winograd_last_variant(void) { return mvdetr::g_winograd_last_variant.load(); }
+
+extern "C" int mvdetr_winograd_set_schedule(int v) { return mvdetr::g_winograd_schedule.exchange(v == 1 || v == 2 ? v : 0); }
+
+extern "C" int mvdetr_winograd_last_schedule(void) { return mvdetr::g_winograd_last_schedule.load(); }
+
+extern "C" int mvdetr_winograd_schedule_of(int C, int K, int dilation) { return mvdetr::wino::schedule_of(C, K, dilation); }
 
 extern "C" int mvdetr_winograd_last_tail_units(void) { return mvdetr::g_winograd_last_tail_units.load(); }
 

@@ -152,6 +152,29 @@ def last_variant() -> int:
     return int(_lib.lib().mvdetr_winograd_last_variant())
 
 
+# (C, K, dilation) whose 8-wave launch runs the de-phased schedule under the default mode: the C library's table
+# (schedule_family in csrc/conv_winograd.hip; tests/test_conv_winograd_schedule.py holds the two together), by the family
+# rule on tools/conv_bench.py --schedule (profiles/conv_winograd_dephase_shapes.txt)
+SCHEDULE_FAMILIES = ((64, 64, 1), (128, 128, 1), (256, 256, 1), (256, 256, 2), (256, 512, 2), (512, 512, 1), (512, 512, 4))
+
+
+def set_winograd_schedule(schedule: int) -> int:
+    """How the 8-wave kernel deals a chunk's loads and input transform to the two waves of a SIMD: 0 (the default) as the C
+    library's table says for the (C, K, dilation); 1 lockstep, one program for all eight waves; 2 de-phased, waves 4-7 on a
+    program of their own.  Anything else means 0.  Returns the previous setting; the bits of the result do not depend on it."""
+    return int(_lib.lib().mvdetr_winograd_set_schedule(int(schedule)))
+
+
+def last_schedule() -> int:
+    """The schedule of the last Winograd convolution: 1 or 2 (0 before the first; 1 where the 4-wave kernel ran)."""
+    return int(_lib.lib().mvdetr_winograd_last_schedule())
+
+
+def schedule_of(C: int, K: int, dilation: int) -> int:
+    """The schedule an 8-wave launch of this shape takes under the current setting: 1 or 2."""
+    return int(_lib.lib().mvdetr_winograd_schedule_of(int(C), int(K), int(dilation)))
+
+
 def last_tail_units() -> int:
     """The units the last Winograd convolution ran as half units (0: it had no second launch)."""
     return int(_lib.lib().mvdetr_winograd_last_tail_units())

@@ -7,6 +7,7 @@ MFMA kernel, interleaved in one process, HIP events.
     python tools/conv_bench.py --epilogue [--out profiles/conv_winograd_epilogue_shapes.txt]
     python tools/conv_bench.py --tail [--out profiles/conv_winograd_w16_shapes.txt]
     python tools/conv_bench.py --variant
+    python tools/conv_bench.py --schedule [--out profiles/conv_winograd_dephase_shapes.txt]
     python tools/conv_bench.py --backward [--out profiles/conv_winograd_backward_shapes.txt]
 
 A repetition times `launches` back-to-back launches of one side, then of the other; a family is switched on in
@@ -25,6 +26,10 @@ repetition of every process run, on both rows.
 
 --variant times the 4-wave persistent kernel (variant 1) against the 8-wave one on 16-channel wave blocks (variant 2) the same
 way; the same rule fills variant2_family.
+
+--schedule times the 8-wave kernel against itself: all eight waves on one program (schedule 1, lockstep) against waves 4-7 on
+a program of their own (schedule 2, de-phased), variant 2 and the default tail on both sides, interleaved; the same rule fills
+schedule_family.
 
 --backward times the training pieces on the eight shapes, each against torch's convolution_backward (cudnn.benchmark) with the
 matching output mask, interleaved: the data gradient alone (the forward kernel on Ut), the weight gradient alone
@@ -208,6 +213,54 @@ def variant_table(args, dev):
     return lines
 
 
+def schedule_table(args, dev):
+    """--schedule: the 8-wave kernel in lockstep (schedule 1) against the de-phased schedule (2), plain store and the shape's
+    first fused store, interleaved."""
+    from mvdetr_amd.ops import conv_winograd as cw
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    lines = [f"# conv3x3_winograd_w16x2_f32 (variant 2 on every shape), schedule 1 (lockstep) vs schedule 2 (de-phased), default tail "
+             f"on both, fp32 channel-last, ms per convolution over {args.launches} launches, {args.reps} interleaved repetitions",
+             "# shape               C->K     d  pixels       store           schedule 1 min/med/max   schedule 2 min/med/max    "
+             "wins   gain us   equal"]
+    for name, C, K, d, modes, pixels in EPILOGUE_SHAPES:
+        N, H, W = pixels or args.pixels
+        torch.manual_seed(C + K + d)
+        conv = nn.Conv2d(C, K, 3, 1, d, d, bias=False)
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+        conv = conv.to(dev).to(memory_format=torch.channels_last).eval()
+        x = torch.randn(N, C, H, W, device=dev).relu_().contiguous(memory_format=torch.channels_last)
+        bn, bn2 = _bn(K, dev), _bn(K, dev)
+        res = torch.randn(N, K, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+        cw.set_winograd_variant(2)
+        for mode in ("none", modes[0]):
+            r, rbn = (None if mode in ("none", "bn") else res), (bn2 if mode == "bn_bn_add" else None)
+            if mode == "none":
+                fn = lambda: cw.winograd_conv3x3(x, conv, force=True)  # noqa: E731
+            else:
+                fn = lambda: cw.winograd_conv3x3_bn_act(x, conv, bn, r, rbn, relu=True, force=True)  # noqa: E731
+            t = [[], []]
+            with torch.no_grad():
+                outs = []
+                for sch in (1, 2):
+                    cw.set_winograd_schedule(sch)
+                    for _ in range(3):
+                        y = fn()
+                    assert cw.last_schedule() == sch and cw.last_variant() == 2
+                    outs.append(y)
+                same = torch.equal(*outs)
+                for _ in range(args.reps):
+                    for side, sch in zip(t, (1, 2)):
+                        cw.set_winograd_schedule(sch)
+                        side.append(timed(fn, args.launches))
+            cw.set_winograd_schedule(0)
+            cols = "     ".join(f"{min(v):6.3f} {med(v):6.3f} {max(v):6.3f}" for v in t)
+            lines.append(f"{name:<20} {C:>4}->{K:<4} {d}  {N}x{H}x{W:<5} {(mode + '_relu') if mode != 'none' else 'plain':<15} "
+                         f"{cols}     {sum(b < a for a, b in zip(*t))}/{args.reps}   {(med(t[0]) - med(t[1])) * 1e3:7.1f}   {same}")
+            print(lines[-1], flush=True)
+        cw.set_winograd_variant(0)
+    return lines
+
+
 def backward_table(args, dev):
     """--backward: dgrad alone, wgrad alone, forward + backward together; Winograd against torch, interleaved."""
     from mvdetr_amd.ops import conv_winograd as cw
@@ -269,6 +322,7 @@ def main():
     ap.add_argument("--epilogue", action="store_true", help="time the convolutions with their epilogues, three sides")
     ap.add_argument("--tail", action="store_true", help="time the last round as whole units against half units")
     ap.add_argument("--variant", action="store_true", help="time the 4-wave persistent kernel against the 8-wave one")
+    ap.add_argument("--schedule", action="store_true", help="time the 8-wave kernel in lockstep against the de-phased schedule")
     ap.add_argument("--backward", action="store_true", help="time the data gradient, the weight gradient and forward + backward")
     args = ap.parse_args()
     from mvdetr_amd.ops import conv_winograd as cw
@@ -282,6 +336,8 @@ def main():
         lines, shapes = tail_table(args, dev), []
     elif args.variant:
         lines, shapes = variant_table(args, dev), []
+    elif args.schedule:
+        lines, shapes = schedule_table(args, dev), []
     elif args.backward:
         lines, shapes = backward_table(args, dev), []
     else:
