@@ -1,6 +1,7 @@
 // What the Winograd F(2x2, 3x3) kernels of conv_winograd.hip (forward) and conv_winograd_backward.hip (weight gradient) share:
 // the tile grid of a shape -- every sub-lattice (y mod d, x mod d) of an image has its own grid of 2x2 output tiles -- the
-// buffer-load constants, and the process-wide bookkeeping behind mvdetr_winograd_last_kernel / _launch_count / _set_max_workgroups.
+// buffer-load constants, the host entries' offset bounds and CU count, and the process-wide bookkeeping behind
+// mvdetr_winograd_last_kernel / _launch_count / _set_max_workgroups.  (The device text they share: conv_winograd_device.h.)
 #pragma once
 #include "common.h"
 
@@ -88,6 +89,27 @@ inline bool tile_shape(Shape &s, int N, int H, int W, int C, int K, int dilation
     s.tiles = (unsigned)tiles;
     s.units = (unsigned)blocks;
     return true;
+}
+
+// A lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
+// 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C and K are multiples of 8, so the bound keeps every offset
+// into x, y or grad_y below 2^32 - 64, under the range of the kernels' buffer resources (X_RANGE)
+inline bool offsets_fit(int H, int W, int C, int K) { return (256 + 2 * (int64_t)H * W) * (C > K ? C : K) < (int64_t)1 << 30; }
+
+// U is staged through a buffer resource too, with 32-bit byte offsets from the slice's first column: 64 C K bytes
+// (mvdetr_winograd_weights_f32 makes no U above 2^26 elements of (c, k))
+inline bool weights_fit(int C, int K) { return (int64_t)C * K < (int64_t)1 << 26; }
+
+// The CUs of the current device: one persistent workgroup each (one fits).  256 where the runtime does not say.
+inline int device_cus()
+{
+    static PerDevice<int> cus_of;
+    return cus_of.get([] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    });
 }
 
 }  // namespace wino

@@ -41,9 +41,13 @@
 //   conv3x3_winograd_w16_f32     HALF units (32 tiles x 64 channels, 4 waves of the same wave block), one per workgroup, for the
 //                          units of a launch's last, mostly empty round: a second launch behind the persistent one.
 //   No atomics, no split over the input channels: the result is deterministic.
-#include "bn_epilogue.h"
+//
+// Where each part lives: conv_winograd.h has the tile grid of a shape, the buffer-load constants and what the two host entries
+// share (offset bounds, CU count); conv_winograd_device.h the chunk's and the store's constants and types and the device functions
+// that all kernels call (out_range / out_window, out_offsets, bn_fold_channel, u_lane_offset); this file the three kernels and the
+// host side: the family table (family_of), make_plan, launch<MODE, RELU> behind a [mode][relu] table, conv_entry, the C ABI.
 #include "common.h"
-#include "conv_winograd.h"
+#include "conv_winograd_device.h"
 #include "../../include/mvdetr_ops.h"
 
 #include <atomic>
@@ -65,7 +69,6 @@ static std::atomic<int> g_winograd_last_schedule{0};
 namespace wino {
 
 // (TILES = 64 tiles and KB = 64 output channels per workgroup, the tile grid and its Shape: conv_winograd.h)
-constexpr int CC = 8;                      // input channels per chunk
 // V in LDS is [channel 8][xi 4][column 72][nu 4]: the four nu of a row xi of one (tile, channel) are one 16-byte slot, written
 // by one ds_write_b128 and read by one ds_read_b128.  The column of tile t in the rows of channel pair cp is t + 2 cp (72
 // columns: 8 of padding), which keeps the four channel pairs that eight lanes write together on different banks and is
@@ -74,26 +77,10 @@ constexpr int CC = 8;                      // input channels per chunk
 constexpr int VCOLS = TILES + 8;
 constexpr int VROW = VCOLS * 4;            // floats per (channel, xi) row of V: 1,152 bytes
 constexpr int V_FLOATS = CC * 4 * VROW;    // 9,216
-constexpr int U_FLOATS = 16 * CC * KB;     // 8,192
 constexpr int BUF_FLOATS = U_FLOATS + V_FLOATS;   // U first: every instruction offset of both stays below 64 KB (V) and
                                                   // 255 rows of 256 bytes (U)
 constexpr int TINFO_SLOTS = 4;             // units whose tiles' output descriptors are kept at a time (a power of two)
 constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4 + TINFO_SLOTS * TILES * 16;      // two buffers + the descriptors = 143,360
-
-// An output element that is not stored, in a tile's descriptor: the lane's channel is added with unsigned saturation, so it
-// stays beyond every range, and a buffer store (or a residual load) at it does nothing
-constexpr unsigned Y_NONE = 0xFFFFFFFFu;
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-// What the output store applies (MODE 0: nothing, and none of this is read).  res has y's [N, H, W, K] geometry.
-struct Epilogue {
-    BnVectors bn, bn2;
-    const float *res;
-};
 
 // MODE 0: y = conv(x).  1: y = act(bn(conv)).  2: act(bn(conv) + res).  3: act(bn(conv) + bn2(res)).  The arithmetic after
 // the convolution is bn_act_cl's (bn_epilogue.h), element for element: the same bits as the pass over a stored y.
@@ -104,7 +91,6 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
     // ONE shared array: two {U, V} buffers, then four units' tiles' output descriptors: the byte offsets of a tile's four
     // outputs from the unit's first image, channel 0 of the unit's block, Y_NONE for one that is not stored
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -360,26 +346,18 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         const int kb = cpl.kb, n0 = cpl.n;
         // y (and the residual) through a buffer resource that starts at the unit's first image and channel and ends with
         // the tensor: a lane's byte offset is its tile's descriptor plus its channel, and Y_NONE plus anything saturates
-        const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
-        const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
-        const __amdgpu_buffer_rsrc_t yrsrc =
-            __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+        const int yrange = out_range(s.N, H, W, K, n0, kb);
+        const __amdgpu_buffer_rsrc_t yrsrc = out_window(y, H, W, K, n0, kb, yrange);
         // accumulator register r holds tile wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5): an instruction offset
         const u32x4 *const ti = tinfo + cslot * TILES + wm * 32 + 4 * (lane >> 5);
         auto offsets = [&](int r, unsigned (&o4)[4]) {
             const u32x4 dsc = ti[(r & 3) + 8 * (r >> 2)];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+out_offsets(dsc, kcol, o4);
         };
         // The BatchNorm constants of channel kb * 64 + kcol, folded when the workgroup's channel block changes: once per
         // launch where the grid is a multiple of kblocks.
         if (MODE >= 1 && kb != kb_folded) {
-            bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
-            if (MODE == 3) {
-                float bt2;
-                bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
-                bt = bt + bt2;
-            }
+            bn_fold_channel<MODE>(ep, kb * KB + kcol, bs, bt, bs2);
             kb_folded = kb;
         }
         // The residual: 4 values per accumulator register, requested four registers' worth at a time and one such batch
@@ -388,9 +366,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_f32(const float *__restr
         // past the buffer's range, for which nothing is read.  The range ends with the tensor.
         float q[2][4][4];
         __amdgpu_buffer_rsrc_t rrsrc;
-        if (MODE >= 2)
-            rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
-                                                      0x00020000);
+        if (MODE >= 2) rrsrc = out_window(ep.res, H, W, K, n0, kb, yrange);
         auto load_res = [&](int b) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
@@ -492,7 +468,6 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_w16_f32(const float *__r
 {
     constexpr int HT = w16::HT, VROW = w16::VROW, BUF_FLOATS = w16::BUF_FLOATS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -542,8 +517,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_w16_f32(const float *__r
 
     // ---- U by LDS-DMA: float f = r * 1024 + tid * 4 of the LDS image is p = 2 r + (tid >> 7), c = (tid >> 4) & 7, column
     // (tid & 15) * 4, which holds output channel (column - 16 (c & 1)) mod 64 of the slice
-    const unsigned uoff =
-        ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + ((((tid & 15) * 4) - 16 * ((tid >> 4) & 1)) & 63)) * 4u;
+    const unsigned uoff = u_lane_offset(tid, C, K);
     const unsigned ustep = 2u * C * K * 4u;
     float raw[16];
     auto load_piece = [&](int c0, float *ubuf, int q) {                       // 16 x loads, then the 8 LDS-DMA of U
@@ -654,12 +628,7 @@ __global__ __launch_bounds__(256) void conv3x3_winograd_w16_f32(const float *__r
     const int kcol = wave * 16 + (lane & 15);
     float bs = 1.f, bt = 0.f, bs2 = 0.f;
     if (MODE >= 1) {
-        bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
-        if (MODE == 3) {
-            float bt2;
-            bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
-            bt = bt + bt2;
-        }
+        bn_fold_channel<MODE>(ep, kb * KB + kcol, bs, bt, bs2);
     }
     const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
     const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
@@ -745,7 +714,6 @@ __device__ __forceinline__ void conv3x3_winograd_w16x2_deal(const float *__restr
                                                             const int wave)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     u32x4 *const tinfo = reinterpret_cast<u32x4 *>(lds + 2 * BUF_FLOATS);
 
     int lane = threadIdx.x & 63;
@@ -820,8 +788,7 @@ __device__ __forceinline__ void conv3x3_winograd_w16x2_deal(const float *__restr
 
     // U by LDS-DMA, 4 x 16 bytes per lane: float f = r * 2048 + tid * 4 of the LDS image is p = 4 r + (tid >> 7), c = (tid >> 4) & 7,
     // column (tid & 15) * 4, which holds output channel (column - 16 (c & 1)) mod 64 (the rotation of the half-unit kernel)
-    const unsigned uoff =
-        ((unsigned)((tid >> 7) * C + ((tid >> 4) & 7)) * K + ((((tid & 15) * 4) - 16 * ((tid >> 4) & 1)) & 63)) * 4u;
+    const unsigned uoff = u_lane_offset(tid, C, K);
     const unsigned ustep = 4u * C * K * 4u;
     float raw[16];
     auto load_x = [&](int c0, int e) {
@@ -985,24 +952,16 @@ __device__ __forceinline__ void conv3x3_winograd_w16x2_deal(const float *__restr
 
             // ---- the store: conv3x3_winograd_f32's, over 2 tile blocks x 4 registers ------------------------------------------------
             const int kb = cpl.kb, n0 = cpl.n;
-            const unsigned long long left = ((unsigned long long)(s.N - n0) * H * W * K - (unsigned)(kb * KB)) * 4ull;
-            const int yrange = (int)(left < X_RANGE ? (unsigned)left : X_RANGE);
-            const __amdgpu_buffer_rsrc_t yrsrc =
-                __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n0 * H * W * K + kb * KB, 0, yrange, 0x00020000);
+            const int yrange = out_range(s.N, H, W, K, n0, kb);
+            const __amdgpu_buffer_rsrc_t yrsrc = out_window(y, H, W, K, n0, kb, yrange);
             // register r of tile block h is tile 32 (w / 4) + 16 h + 4 (lane >> 4) + r
             const u32x4 *const ti = tinfo + cslot * TILES + th * 32 + 4 * (lane >> 4);
             auto offsets = [&](int b, unsigned (&o4)[4]) {
                 const u32x4 dsc = ti[16 * (b >> 2) + (b & 3)];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = __builtin_elementwise_add_sat(dsc[e], (unsigned)kcol * 4u);
+out_offsets(dsc, kcol, o4);
             };
             if (MODE >= 1 && kb != kb_folded) {
-                bn_fold1(ep.bn, kb * KB + kcol, bs, bt);
-                if (MODE == 3) {
-                    float bt2;
-                    bn_fold1(ep.bn2, kb * KB + kcol, bs2, bt2);
-                    bt = bt + bt2;
-                }
+                bn_fold_channel<MODE>(ep, kb * KB + kcol, bs, bt, bs2);
                 kb_folded = kb;
             }
             // the second block's residual: behind the first block's first row, or (a role copy with two BatchNorms, which has a
@@ -1010,9 +969,7 @@ __device__ __forceinline__ void conv3x3_winograd_w16x2_deal(const float *__restr
             constexpr int RES1_AT = ROLES && MODE == 3 ? 2 : 0;
             float q[2][4][4];                                                     // the residual of one tile block, one block ahead
             __amdgpu_buffer_rsrc_t rrsrc;
-            if (MODE >= 2)
-                rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ep.res + (size_t)n0 * H * W * K + kb * KB), 0, yrange,
-                                                          0x00020000);
+            if (MODE >= 2) rrsrc = out_window(ep.res, H, W, K, n0, kb, yrange);
             auto load_res = [&](int h) {
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
@@ -1152,42 +1109,31 @@ static bool bn_ok(const BnVectors &b)
     return b.mean && b.var && aligned(b.mean, 4) && aligned(b.var, 4) && aligned(b.gamma, 4) && aligned(b.beta, 4);
 }
 
-// The (C, K, dilation) whose last round runs as half units under tail mode 1: those on which it measured faster in every
-// repetition of tools/conv_bench.py --tail (profiles/conv_winograd_w16_shapes.txt)
-static bool tail_family(int C, int K, int d)
-{
-    static const int table[][3] = {{64, 64, 1}, {128, 128, 1}, {128, 256, 1}, {256, 256, 1}, {256, 256, 2}, {512, 512, 1}};
-    for (const auto &f : table)
-        if (f[0] == C && f[1] == K && f[2] == d) return true;
-    return false;
-}
+// What the modes 0 / 1 of the three setters choose for a (C, K, dilation): each flag is set where that side measured faster in
+// every repetition of tools/conv_bench.py; a shape that is not listed has none.
+//   tail        the last round runs as half units (--tail, profiles/conv_winograd_w16_shapes.txt)
+//   eight_wave  the persistent launch is the 8-wave kernel (--variant, the same file)
+//   dephased    an 8-wave launch runs the de-phased schedule (--schedule, profiles/conv_winograd_dephase_shapes.txt)
+struct Family {
+    int C, K, d;
+    bool tail, eight_wave, dephased;
+};
 
-// The (C, K, dilation) whose persistent launch is the 8-wave kernel under variant mode 0: those on which it measured faster
-// than the 4-wave kernel in every repetition of tools/conv_bench.py --variant (profiles/conv_winograd_w16_shapes.txt)
-static bool variant2_family(int C, int K, int d)
+static Family family_of(int C, int K, int d)
 {
-    static const int table[][3] = {{64, 64, 1},  {128, 128, 1}, {128, 256, 1}, {256, 256, 1},
-                                   {256, 256, 2}, {256, 512, 2}, {512, 512, 1}, {512, 512, 4}};
-    for (const auto &f : table)
-        if (f[0] == C && f[1] == K && f[2] == d) return true;
-    return false;
-}
-
-// The (C, K, dilation) whose 8-wave launch runs the de-phased schedule under schedule mode 0: those on which it measured faster
-// than lockstep in every repetition of tools/conv_bench.py --schedule (profiles/conv_winograd_dephase_shapes.txt)
-static bool schedule_family(int C, int K, int d)
-{
-    static const int table[][3] = {{64, 64, 1}, {128, 128, 1}, {256, 256, 1}, {256, 256, 2}, {256, 512, 2}, {512, 512, 1}, {512, 512, 4}};
-    for (const auto &f : table)
-        if (f[0] == C && f[1] == K && f[2] == d) return true;
-    return false;
+    static const Family table[] = {{64, 64, 1, true, true, true},    {128, 128, 1, true, true, true},  {128, 256, 1, true, true, false},
+                                   {256, 256, 1, true, true, true},  {256, 256, 2, true, true, true},  {256, 512, 2, false, true, true},
+                                   {512, 512, 1, true, true, true},  {512, 512, 4, false, true, true}};
+    for (const Family &f : table)
+        if (f.C == C && f.K == K && f.d == d) return f;
+    return Family{C, K, d, false, false, false};
 }
 
 // The schedule of an 8-wave launch of this shape under the current mode: 1 lockstep, 2 de-phased
 static int schedule_of(int C, int K, int d)
 {
     const int v = g_winograd_schedule.load();
-    return v ? v : schedule_family(C, K, d) ? 2 : 1;
+    return v ? v : family_of(C, K, d).dephased ? 2 : 1;
 }
 
 // How a call is split: G persistent workgroups run the units [0, R G) and, where the rest is a tail, 2 rem half units run
@@ -1206,11 +1152,12 @@ static Plan make_plan(const Shape &s, int cus)
     if (cap > 0 && p.G > (unsigned)cap) p.G = (unsigned)cap;
     p.R = s.units / p.G;
     p.rem = s.units % p.G;
+    const Family f = family_of(s.C, s.K, s.d);
     const int tail = g_winograd_tail.load();
-    const bool on = p.rem > 0 && (tail == 2 || (tail == 1 && 2 * p.rem <= p.G && tail_family(s.C, s.K, s.d)));
+    const bool on = p.rem > 0 && (tail == 2 || (tail == 1 && 2 * p.rem <= p.G && f.tail));
     p.half_units = on ? 2 * p.rem : 0;
     const int v = g_winograd_variant.load();
-    p.variant = v ? v : variant2_family(s.C, s.K, s.d) ? 2 : 1;
+    p.variant = v ? v : f.eight_wave ? 2 : 1;
     return p;
 }
 
@@ -1218,19 +1165,13 @@ static Plan make_plan(const Shape &s, int cus)
 static int conv_entry(const float *x, const float *U, float *y, int N, int H, int W, int C, int K, int dilation, int mode,
                       bool relu, const Epilogue &ep, void *stream)
 {
-    if (!x || !U || !y || x == y || N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    if (!x || !U || !y || x == y || N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || mode < 0 || mode > 3) return (int)hipErrorInvalidValue;
     if (mode >= 1 && !bn_ok(ep.bn)) return (int)hipErrorInvalidValue;
     if (mode == 3 && !bn_ok(ep.bn2)) return (int)hipErrorInvalidValue;
     if (C % 8 != 0 || K % 64 != 0 || !(dilation == 1 || dilation == 2 || dilation == 4) || !aligned(x, 16) ||
         !aligned(U, 16) || !aligned(y, 16) || (mode >= 2 && !aligned(ep.res, 16)))
         return (int)hipErrorNotSupported;
-    // a lane's byte offsets are 32-bit and count from the image of its workgroup's first tile: 64 tiles span at most
-    // 256 / (H W) + 2 images (a tile covers at most 4 pixels of one).  C is a multiple of 8, so the bound keeps every
-    // offset below 2^32 - 64, under the range of the kernel's x buffer (wino::X_RANGE)
-    if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return (int)hipErrorNotSupported;
-    // U is staged through a buffer resource too, with 32-bit byte offsets from the slice's first column: 64 C K bytes
-    // (mvdetr_winograd_weights_f32 makes no U above 2^26 elements of (c, k))
-    if ((int64_t)C * K >= (int64_t)1 << 26) return (int)hipErrorNotSupported;
+    if (!offsets_fit(H, W, C, K) || !weights_fit(C, K)) return (int)hipErrorNotSupported;
     if (mode >= 2) {
         // the residual is read while other workgroups store y: their byte ranges may not meet
         const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep.res), y0 = reinterpret_cast<uintptr_t>(y);
@@ -1242,14 +1183,7 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     if (!tile_shape(s, N, H, W, C, K, dilation)) return (int)hipErrorNotSupported;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // the persistent grid: one workgroup per CU (one fits), each running every G-th unit; fewer under the tests' cap
-    static PerDevice<int> cus_of;
-    const int cus = cus_of.get([] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    });
-    const Plan pl = make_plan(s, cus);
+    const Plan pl = make_plan(s, device_cus());
     const unsigned nb = pl.G;
     if (pl.half_units) s.units = pl.R * pl.G;                                 // what the persistent kernel runs; the tail starts there
     // the stride from a workgroup's unit to its next one (nb units on), over the tile grid
@@ -1264,11 +1198,12 @@ static int conv_entry(const float *x, const float *U, float *y, int N, int H, in
     stride(nb / (unsigned)s.kblocks + 1, s.dX1, s.dY1, s.dn1);
     const unsigned tu = pl.half_units / 2;
     const int sch = pl.variant == 2 ? schedule_of(C, K, dilation) : 1;       // the 4-wave kernel has one program
-    int rc;
-    if (mode == 0) rc = launch<0, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
-    else if (mode == 1) rc = relu ? launch<1, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<1, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
-    else if (mode == 2) rc = relu ? launch<2, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<2, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
-    else rc = relu ? launch<3, true>(st, nb, x, U, y, s, ep, pl.variant, sch, tu) : launch<3, false>(st, nb, x, U, y, s, ep, pl.variant, sch, tu);
+    // [mode][relu]; mode 0 has no activation
+    static constexpr decltype(&launch<0, false>) kLaunch[4][2] = {{launch<0, false>, launch<0, false>},
+                                                                  {launch<1, false>, launch<1, true>},
+                                                                  {launch<2, false>, launch<2, true>},
+                                                                  {launch<3, false>, launch<3, true>}};
+    const int rc = kLaunch[mode][relu ? 1 : 0](st, nb, x, U, y, s, ep, pl.variant, sch, tu);
     if (rc != 0) return rc;
     g_winograd_last_tail_units = (int)tu;
     g_winograd_last_variant = pl.variant;

@@ -26,7 +26,7 @@
 //   winograd_wgrad_reduce_f32    sums the S slices in index order and writes gw.  No atomics anywhere: for a given S the result
 //                                is bit-identical from call to call.
 #include "common.h"
-#include "conv_winograd.h"
+#include "conv_winograd_device.h"
 #include "../../include/mvdetr_ops.h"
 
 #include <type_traits>
@@ -44,9 +44,6 @@ constexpr int CB = 64;                     // channels of a unit, input and outp
 constexpr int OP_FLOATS = CT * 4 * CB * 4; // one operand of a chunk, [tile][xi][channel][nu]: 8,192 floats
 constexpr int BUF_FLOATS = 2 * OP_FLOATS;  // dM first, then V
 constexpr int LDS_BYTES = 2 * BUF_FLOATS * 4;                                 // two buffers = 131,072
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // How a call is split (make_plan): `units` blocks of 64 x 64 channels, `chunks` chunks of 8 tiles, S splits of `per` chunks
 // each (the last one `last`); the grid runs the units * S items round-robin
@@ -289,26 +286,13 @@ static bool shape_ok(int C, int K, int dilation) { return C % CB == 0 && K % CB 
 // The bounds on a shape, the forward's: 32-bit byte offsets from the image of a chunk's first tile, fewer than 2^31 tiles
 static bool bounds_ok(Shape &s, int N, int H, int W, int C, int K, int dilation)
 {
-    if ((256 + 2 * (int64_t)H * W) * (C > K ? C : K) >= (int64_t)1 << 30) return false;
-    if ((int64_t)C * K >= (int64_t)1 << 26) return false;
-    return tile_shape(s, N, H, W, C, K, dilation);
+    return offsets_fit(H, W, C, K) && weights_fit(C, K) && tile_shape(s, N, H, W, C, K, dilation);
 }
 
 static bool overlap(const void *p, uint64_t pbytes, const void *q, uint64_t qbytes)
 {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
     return a < b + qbytes && b < a + pbytes;
-}
-
-static int device_cus()
-{
-    static PerDevice<int> cus_of;
-    return cus_of.get([] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    });
 }
 
 static int entry(const float *x, const float *gy, float *gw, int N, int H, int W, int C, int K, int dilation, void *workspace,

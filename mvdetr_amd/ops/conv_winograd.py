@@ -126,7 +126,7 @@ def set_winograd_max_workgroups(n: int) -> int:
     return int(_lib.lib().mvdetr_winograd_set_max_workgroups(int(n)))
 
 
-# (C, K, dilation) whose last round runs as half units under the default tail mode: the C library's table (tail_family in
+# (C, K, dilation) whose last round runs as half units under the default tail mode: the C library's table (the tail flag of family_of in
 # csrc/conv_winograd.hip; tests/test_conv_winograd_plan.py holds the two together), by the family rule on
 # tools/conv_bench.py --tail (profiles/conv_winograd_w16_shapes.txt)
 TAIL_FAMILIES = ((64, 64, 1), (128, 128, 1), (128, 256, 1), (256, 256, 1), (256, 256, 2), (512, 512, 1))
@@ -153,7 +153,7 @@ def last_variant() -> int:
 
 
 # (C, K, dilation) whose 8-wave launch runs the de-phased schedule under the default mode: the C library's table
-# (schedule_family in csrc/conv_winograd.hip; tests/test_conv_winograd_schedule.py holds the two together), by the family
+# (the dephased flag of family_of in csrc/conv_winograd.hip; tests/test_conv_winograd_schedule.py holds the two together), by the family
 # rule on tools/conv_bench.py --schedule (profiles/conv_winograd_dephase_shapes.txt)
 SCHEDULE_FAMILIES = ((64, 64, 1), (128, 128, 1), (256, 256, 1), (256, 256, 2), (256, 512, 2), (512, 512, 1), (512, 512, 4))
 

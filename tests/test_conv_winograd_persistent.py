@@ -28,6 +28,7 @@ def test_the_hook_is_declared_bound_and_exported():
 
 def test_one_kernel_and_no_work_counter():
     """The persistent kernel replaced the one-unit kernel (no second copy), and hands out units statically."""
-    src = open(os.path.join(ROOT, "mvdetr_amd", "csrc", "conv_winograd.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "mvdetr_amd", "csrc", f)).read()    # the kernels and the device text they share
+                  for f in ("conv_winograd.hip", "conv_winograd_device.h"))
     assert len(re.findall(r"__global__[^;{]*\bconv3x3_winograd_f32\s*\(", src)) == 1
     assert "gridDim.x" in src and not re.search(r"\batomic(Add|Inc|CAS)\b", src)

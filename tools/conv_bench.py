@@ -21,15 +21,15 @@ sizes; the same rule decides about them: (c) faster than (a) in every repetition
 
 --tail times the Winograd kernel against itself on the eight shapes, plain and with the first epilogue of each shape in its
 store: the last round as whole units in the persistent kernel (tail mode 0) against half units in a second launch (mode 2),
-interleaved.  A shape's tail is switched on (tail_family in csrc/conv_winograd.hip) only where mode 2 is faster in every
+interleaved.  A shape's tail is switched on (the tail flag of family_of in csrc/conv_winograd.hip) only where mode 2 is faster in every
 repetition of every process run, on both rows.
 
 --variant times the 4-wave persistent kernel (variant 1) against the 8-wave one on 16-channel wave blocks (variant 2) the same
-way; the same rule fills variant2_family.
+way; the same rule sets the eight_wave flag.
 
 --schedule times the 8-wave kernel against itself: all eight waves on one program (schedule 1, lockstep) against waves 4-7 on
 a program of their own (schedule 2, de-phased), variant 2 and the default tail on both sides, interleaved; the same rule fills
-schedule_family.
+the dephased flag.
 
 --backward times the training pieces on the eight shapes, each against torch's convolution_backward (cudnn.benchmark) with the
 matching output mask, interleaved: the data gradient alone (the forward kernel on Ut), the weight gradient alone
